@@ -4,7 +4,10 @@
 Q=100, P=160000, 2 clips per GPU (BASELINE.json configs[3] shapes; forward+loss as BASELINE.json:metric says), encoder
 dropout 0.3 as every shipped config sets it (MODEL.MASK_FORMER.DROPOUT).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the timed path computed in its last timed step to DIR/<name>.npy (capture_outputs); the inputs,
+weights and seeds are fixed, so two builds run with the same arguments can be compared array for array.
 
 N > 1: one rank per GPU over RCCL.  Launched by `python -m torch.distributed.run ... bench.py --gpus N ...` the ranks read
 RANK / LOCAL_RANK / WORLD_SIZE; launched plainly with --gpus N > 1 this script starts those N ranks itself (child
@@ -186,6 +189,37 @@ def calibrate_teacher(model, images, want=10):
         bias = model.teacher[1].predictor.class_embed.bias
         bias[0] += (need - thr) / 2
         bias[1] -= (need - thr) / 2
+
+
+DUMP_BYTES = 64 * 2 ** 20            # --dump-outputs: at most this much in all
+MASK_SAMPLE = 2 ** 21                # mask-logit values kept when the full maps do not fit in half of it
+
+
+def capture_outputs(model, losses, total):
+    """what the timed step computed, as host arrays {name: float32 / float64 ndarray}: the weighted loss dict
+    KDVideoMaskFormer.forward_losses returns (one scalar per loss), their total, and the student's final prediction heads
+    (model.last): class logits [B,Q,K+1] in full, mask logits [B,Q,T,hm,wm] in full when they fit in half the budget, otherwise a
+    fixed seeded sample of their flat values with its indices"""
+    out = {k: v.detach().float().cpu().numpy() for k, v in losses.items()}
+    out["loss_total"] = total.detach().float().cpu().numpy()
+    st = model.last["student"]
+    st = st if isinstance(st, list) else [st]            # the clip pipeline keeps one MaskOutputs per clip
+    out["pred_logits"] = torch.cat([s.class_logits[-1] for s in st]).float().cpu().numpy()
+    pm = torch.cat([s.pred_masks(-1) for s in st]).float()
+    if pm.numel() * 4 <= DUMP_BYTES // 2:
+        out["pred_masks"] = pm.cpu().numpy()
+    else:
+        idx = np.unique(np.random.default_rng(0).integers(0, pm.numel(), MASK_SAMPLE))
+        out["pred_masks_sample"] = pm.reshape(-1)[torch.from_numpy(idx).to(pm.device)].cpu().numpy()
+        out["pred_masks_sample_index"] = idx.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES
+    return out
+
+
+def write_outputs(d, outputs):
+    os.makedirs(d, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def _usable_cores():
@@ -471,7 +505,12 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the multi-rank control flow (spawn, rendezvous, barrier, max-over-ranks, one JSON line): no GPU "
                          "work, value null")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step (rank 0) to DIR/<name>.npy: "
+                         "the weighted losses, their total, the student's final class logits and mask logits (a fixed sample if large)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -527,8 +566,7 @@ def main():
         # into padded target planes (prepare_targets), both forwards, both criteria, the weighted sum the trainer takes
         images = ops.normalize_pad(frames, 32, mean, std)
         targets = TargetSet.from_list(masks, device=dev)
-        losses = model.forward_losses(images, targets)
-        return sum(losses.values())
+        return model.forward_losses(images, targets)
 
     def seeded_step(two_streams):
         model.overlap_teacher = model.overlap_criteria = two_streams
@@ -555,21 +593,26 @@ def main():
             ops.PROFILE = []
         t0 = time.perf_counter()
         for _ in range(steps):
-            tot = step()
+            losses = step()
+            tot = sum(losses.values())
             totals.append(tot)
         _fence(world)
         el = time.perf_counter() - t0
         pr, ops.PROFILE = ops.PROFILE, None
         STEP_TOTALS[two_streams] = totals
+        STEP_LOSSES[two_streams] = losses
         return el, tot, pr
 
     STEP_TOTALS = {}
+    STEP_LOSSES = {}                                     # the loss dict of each schedule's last timed step
 
     two = not args.one_stream
     live_events = not args.no_kernel_events and not two
     dt, total, prof = timed(live_events, two, args.steps, args.warmup)
     dt = _max_over_ranks(dt, world, cdev or dev)
     assert bool(torch.isfinite(total)), "non-finite loss"
+    # taken now: every later pass overwrites the model's last outputs
+    outputs = capture_outputs(model, STEP_LOSSES[two], total) if args.dump_outputs and rank == 0 else None
     # the other schedule, timed the same way after the metric, and a bitwise comparison of all 42 losses between the two
     # schedules on the same seeds (every kernel is deterministic, so the schedule must not change a bit)
     dt_other, prof_other, same = float("nan"), None, None
@@ -624,16 +667,21 @@ def main():
     fallback = False
     if same is False and two and dt_other == dt_other:
         # The two schedules must agree bit for bit (every kernel is deterministic).  If they do not, the two-stream timing is not
-        # reported as the metric: the line carries the one-stream measurement (fewer steps, same kind) and says so.
+        # reported as the metric: the one-stream schedule is timed again over --steps steps, the line carries that measurement
+        # (and its outputs) and says so.
         sys.stderr.write("bench.py: losses differ between the two-stream and the one-stream schedule -- reporting the one-stream time\n")
         fallback = True
+        other_ms = 1000 * dt / args.steps
+        two = False
+        dt, total, _ = timed(False, two, args.steps, args.warmup)
+        dt = _max_over_ranks(dt, world, cdev or dev)
+        outputs = capture_outputs(model, STEP_LOSSES[two], total) if args.dump_outputs and rank == 0 else None
+    else:
+        other_ms = 1000 * dt_other / max(args.steps // 2, 2)
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     if rank == 0:
         frames_per_step = world * B * T
-        other_ms = 1000 * dt_other / max(args.steps // 2, 2)
-        if fallback:
-            steps_other = max(args.steps // 2, 2)
-            dt, dt_other, other_ms = dt_other * args.steps / steps_other, dt, 1000 * dt / args.steps
-            two = False
         res = {"metric": "clip-frames/sec fwd+loss, R50 M2F-Video T=8 720p Q=100", "value": round(frames_per_step * args.steps / dt, 3),
                "unit": "clip-frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": round(1000 * dt / args.steps, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -710,6 +758,9 @@ def main():
                                             "frac_net_of_skipped_teacher_masks": round(res["value"] / world * net / 8000.0, 4)})
         if amp_res is not None:
             res["amp"] = amp_res
+        if outputs is not None:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": len(outputs),
+                                     "bytes": int(sum(a.nbytes for a in outputs.values()))}
         if prof and args.dense_breakdown:
             import collections
             agg = collections.defaultdict(lambda: [0, 0.0, 0.0])

@@ -128,6 +128,38 @@ def test_bench_two_ranks_share_the_gpu_gloo():
     assert ts["n_gpus"] == 2 and ts["allreduce_bytes"] > 100e6 and ts["ms_per_iteration"] > 0
 
 
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """bench.py --dump-outputs: two runs with the same arguments write the same arrays, bit for bit (float32 / float64, within
+    the budget); the line reports the --steps timed steps and ms_per_step; loss_total is the sum of the dumped losses"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for name in ("a", "b"):
+        d = str(tmp_path / name)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "tiny", "--steps", "3", "--warmup", "1",
+                            "--no-cpu-baseline", "--no-train-step", "--no-keymask", "--dump-outputs", d],
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        runs.append((d, json.loads(lines[0])))
+    (da, ja), (db, _) = runs
+    assert ja["steps"] == 3 and ja["ms_per_step"] > 0
+    names = sorted(os.listdir(da))
+    assert names == sorted(os.listdir(db)) and ja["dumped_outputs"]["arrays"] == len(names)
+    assert {"loss_total.npy", "pred_logits.npy", "pred_masks.npy", "loss_ce.npy", "kd_loss_dice.npy"} <= set(names)
+    arrays = {n[:-4]: (np.load(os.path.join(da, n)), np.load(os.path.join(db, n))) for n in names}
+    assert sum(a.nbytes for a, _ in arrays.values()) <= 64 * 2 ** 20
+    for n, (a, b) in arrays.items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), n
+    losses = [a for n, (a, _) in arrays.items() if "loss_" in n and n != "loss_total"]
+    np.testing.assert_allclose(arrays["loss_total"][0], np.sum(losses, dtype=np.float64), rtol=1e-5)
+
+
 def test_train_step_at_config4_gradients_finite_and_reproducible(setup):
     """BASELINE configs[3]'s training leg at full size (no autograd oracle fits there): every one of the 345 student gradients
     is finite, and two iterations on the same batch with the same seeds agree bit for bit (no float atomics are left in the step:
