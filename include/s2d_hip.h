@@ -431,6 +431,28 @@ long s2d_rle_string_workspace_bytes(long ncounts);
 int s2d_rle_strings_u8(const int *positions, const long *frame_off, int F, long hw, long ncounts, void *workspace,
                        long workspace_bytes, uint8_t *chars, long *str_off, hipStream_t stream);
 
+/* ---- YTVIS video-instance evaluation (s2d_amd/ytvis_eval.py; ytvoseval.py:176-222 computeIoU, ytvos.py:239-252 areas) -- */
+
+/* pycocotools rleFrString (third party, restated) of F COCO RLE strings at once, one wave per string: string f is
+ * chars[str_off[f] .. str_off[f+1]); its run ENDS (running sums of the counts, clamped to hw = H*W) go to
+ * ends[str_off[f] + j], and nrun[f] = its number of runs.  Only frames with nrun[f] < 0 on entry are parsed: the others
+ * already hold their ends (uncompressed RLE, prefixed on the host) or are absent (nrun = 0). */
+int s2d_rle_parse_strings(const uint8_t *chars, const long *str_off, int F, long hw, int *ends, int *nrun, hipStream_t stream);
+
+/* run ends (frame f: ends[run_off[f] .. + nrun[f]), column-major runs, the first one of zeros) -> bit planes
+ * bits [F][ceil(H*W/32)] (row-major flat index i -> word i/32, bit i%32, tail bits zero: the s2d_pack_mask_bits_u8 layout
+ * for planes of n = H*W).  A frame with nrun = 0 is an all-zero plane.  bits is zeroed by the call. */
+int s2d_rle_decode_bits(const int *ends, const long *run_off, const int *nrun, int F, int H, int W, uint32_t *bits,
+                        hipStream_t stream);
+
+/* area[f] = popcount of plane f of bits [F][words_per_plane] (mask_util.area) */
+int s2d_mask_plane_areas_u32(const uint32_t *bits, int F, long words_per_plane, unsigned *area, hipStream_t stream);
+
+/* inter[d][g] = sum over words of popcount(a[d] & b[g]) for D tracks a [D][words] against G tracks b [G][words] (a track =
+ * its T frame planes back to back); inter [D][G] u64, zeroed by the call.  The D x G block of s2d_mask_pair_counts_u64. */
+int s2d_mask_cross_counts_u64(const uint32_t *a, int D, const uint32_t *b, int G, long words, unsigned long long *inter,
+                              hipStream_t stream);
+
 /* ---- gradients of the dense layers: HBM-bound helpers around s2d_gemm_nt_f32 ----------- */
 
 /* Weight-gradient contraction without transposed copies: C_slices[s][n][k] = sum over the rows m of slice s of
