@@ -448,10 +448,32 @@ int s2d_rle_decode_bits(const int *ends, const long *run_off, const int *nrun, i
 /* area[f] = popcount of plane f of bits [F][words_per_plane] (mask_util.area) */
 int s2d_mask_plane_areas_u32(const uint32_t *bits, int F, long words_per_plane, unsigned *area, hipStream_t stream);
 
+/* bbox [F][4] int = x, y, w, h of plane f of bits [F][words_per_plane] (words_per_plane = ceil(H*W/32), the layout above):
+ * pycocotools rleToBbox (mask_util.toBbox) semantics, the tight box of the set pixels, 0,0,0,0 for an empty plane.  The
+ * bboxes of the pseudo annotations written from a results.json (keymask_ident/convert_results_to_annotations.py:72). */
+int s2d_mask_plane_bbox_u32(const uint32_t *bits, int F, int H, int W, long words_per_plane, int *bbox, hipStream_t stream);
+
 /* inter[d][g] = sum over words of popcount(a[d] & b[g]) for D tracks a [D][words] against G tracks b [G][words] (a track =
  * its T frame planes back to back); inter [D][G] u64, zeroed by the call.  The D x G block of s2d_mask_pair_counts_u64. */
 int s2d_mask_cross_counts_u64(const uint32_t *a, int D, const uint32_t *b, int G, long words, unsigned long long *inter,
                               hipStream_t stream);
+
+/* ---- test-time frame resize (s2d_amd/data/resize.py, data/test_loader.py): detectron2 ResizeTransform.apply_image =
+ * PIL Image.resize(BILINEAR) on uint8 RGB frames, bit-exact ------------------------------------------------------------- */
+
+/* LDS bytes of one s2d_resize_bilinear_u8 workgroup for a plan (rows_max input rows, span_q 16-byte chunks per staged row,
+ * kh horizontal taps); a plan is launchable when this is <= 65536. */
+long s2d_resize_lds_bytes(int rows_max, int span_q, int kh);
+
+/* T frames src u8 [T][H0][W0][3] (HWC RGB) -> dst u8 [T][3][H1][W1] (CHW).  Per axis, PIL's coefficient table built on the host:
+ * bounds int [out][2] = (first input index, tap count), coeffs int [out][k] = 22-bit fixed-point weights (k = kh / kv columns);
+ * an axis of unchanged size takes the identity table (1 tap of weight 2^22).  Both tables are monotone (first index and first
+ * index + count never decrease).  Horizontal pass first into a u8 intermediate, then vertical; every output is
+ * clip8((2^21 + sum w * p) >> 22).  Launch plan: band_rows output rows per workgroup, rows_max >= input rows any band reaches,
+ * span_q >= 16-byte chunks any 64-column tile's input span (from a 16-byte-aligned address) covers. */
+int s2d_resize_bilinear_u8(const uint8_t *src, int T, int H0, int W0, const int *h_bounds, const int *h_coeffs, int kh,
+                           const int *v_bounds, const int *v_coeffs, int kv, int H1, int W1, int band_rows, int rows_max,
+                           int span_q, uint8_t *dst, hipStream_t stream);
 
 /* ---- gradients of the dense layers: HBM-bound helpers around s2d_gemm_nt_f32 ----------- */
 

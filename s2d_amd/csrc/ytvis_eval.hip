@@ -156,6 +156,56 @@ __global__ __launch_bounds__(256) void plane_popcount_kernel(const uint32_t *__r
     if (threadIdx.x == 0) area[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
+// bbox[f] = [x, y, w, h] of plane f: pycocotools rleToBbox (third party, restated; what mask_util.toBbox returns for the pseudo
+// annotations of keymask_ident/convert_results_to_annotations.py:72).  rleToBbox takes the extremes of the first and last pixel
+// of every run of ones (column-major), and sets the row range to [0, H-1] when a run starts in one column and ends in a later one.
+// Such a run holds pixel (H-1, c) and pixel (0, c+1), so that row range is the tight one as well: the box is the tight box of the
+// set pixels, [0, 0, 0, 0] for an empty plane.  Each thread walks its words row segment by row segment (a word spans
+// ceil(32 / W) + 1 rows at most); one workgroup per plane.
+__global__ __launch_bounds__(256) void plane_bbox_kernel(const uint32_t *__restrict__ bits, int H, int W, long wpf, int *__restrict__ bbox)
+{
+    __shared__ int red[4][4];
+    const uint32_t *pl = bits + (long)blockIdx.x * wpf;
+    int x_lo = 0x7fffffff, y_lo = 0x7fffffff, x_hi = -1, y_hi = -1;
+    for (long w = threadIdx.x; w < wpf; w += 256) {
+        uint32_t v = pl[w];
+        if (!v) continue;
+        const long p = w * 32;
+        int y = (int)(p / W), c = (int)(p - (long)y * W);
+        int used = 0;
+        while (v) {
+            const int len = 32 - used < W - c ? 32 - used : W - c;
+            const uint32_t seg = len >= 32 ? v : (v & ((1u << len) - 1u));
+            if (seg) {
+                const int lo = __builtin_ctz(seg), hi = 31 - __builtin_clz(seg);
+                x_lo = min(x_lo, c + lo); x_hi = max(x_hi, c + hi);
+                y_lo = min(y_lo, y); y_hi = max(y_hi, y);
+            }
+            v = len >= 32 ? 0u : v >> len;
+            used += len; c = 0; ++y;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        x_lo = min(x_lo, __shfl_xor(x_lo, o, 64)); y_lo = min(y_lo, __shfl_xor(y_lo, o, 64));
+        x_hi = max(x_hi, __shfl_xor(x_hi, o, 64)); y_hi = max(y_hi, __shfl_xor(y_hi, o, 64));
+    }
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[wv][0] = x_lo; red[wv][1] = y_lo; red[wv][2] = x_hi; red[wv][3] = y_hi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < 4; ++i) {
+            x_lo = min(x_lo, red[i][0]); y_lo = min(y_lo, red[i][1]); x_hi = max(x_hi, red[i][2]); y_hi = max(y_hi, red[i][3]);
+        }
+        int *b = bbox + 4L * blockIdx.x;
+        if (x_hi < 0) {
+            b[0] = b[1] = b[2] = b[3] = 0;
+        } else {
+            b[0] = x_lo; b[1] = y_lo; b[2] = x_hi - x_lo + 1; b[3] = y_hi - y_lo + 1;
+        }
+    }
+}
+
 constexpr int CT = 8;
 __global__ __launch_bounds__(256) void cross_count_kernel(const uint32_t *__restrict__ a, int D, const uint32_t *__restrict__ b, int G,
                                                           long words, int ntg, unsigned long long *__restrict__ inter)
@@ -230,6 +280,15 @@ int s2d_mask_plane_areas_u32(const uint32_t *bits, int F, long words_per_plane, 
     if (F < 0 || words_per_plane < 1) return S2D_ERR_ARG;
     if (F == 0) return S2D_OK;
     hipLaunchKernelGGL(plane_popcount_kernel, dim3(F), dim3(256), 0, stream, bits, words_per_plane, area);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_mask_plane_bbox_u32(const uint32_t *bits, int F, int H, int W, long words_per_plane, int *bbox, hipStream_t stream)
+{
+    if (F < 0 || H < 1 || W < 1 || (long)H * W >= (1L << 31) || words_per_plane != ((long)H * W + 31) / 32) return S2D_ERR_ARG;
+    if (F == 0) return S2D_OK;
+    hipLaunchKernelGGL(plane_bbox_kernel, dim3(F), dim3(256), 0, stream, bits, H, W, words_per_plane, bbox);
     S2D_CHECK_LAUNCH();
     return S2D_OK;
 }

@@ -16,6 +16,16 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def shortest_edge_shape(h, w, short_edge_length, max_size):
+    """(h, w) -> (newh, neww): ResizeShortestEdge.get_output_shape (detectron2, augmentation.py:51-75's resize rule)"""
+    scale = short_edge_length * 1.0 / min(h, w)
+    newh, neww = (short_edge_length, scale * w) if h < w else (scale * h, short_edge_length)
+    if max(newh, neww) > max_size:
+        s2 = max_size * 1.0 / max(newh, neww)
+        newh, neww = newh * s2, neww * s2
+    return int(newh + 0.5), int(neww + 0.5)
+
+
 class ClipAugmentation:
     """configuration of build_augmentation(cfg, is_train=True), augmentation.py:116-158"""
 
@@ -55,12 +65,7 @@ class ClipAugmentation:
                     size = int(rng.randint(self.min_size[0], self.min_size[1] + 1))
                 else:
                     size = int(rng.choice(self.min_size))
-            scale = size * 1.0 / min(ch, cw)
-            newh, neww = (size, scale * cw) if ch < cw else (scale * ch, size)
-            if max(newh, neww) > self.max_size:
-                s2 = self.max_size * 1.0 / max(newh, neww)
-                newh, neww = newh * s2, neww * s2
-            neww, newh = int(neww + 0.5), int(newh + 0.5)
+            newh, neww = shortest_edge_shape(ch, cw, size, self.max_size)
             if out_hw is None:
                 out_hw = (newh, neww)
             H1, W1 = out_hw                                  # one output size per clip (frames of a clip are stacked downstream)

@@ -1,0 +1,106 @@
+"""Eval-only driver: `train_net_video.py --eval-only` without detectron2.
+
+    python -m s2d_amd.evaluate --config-file X.yaml --gt ann.json --image-root DIR --output-dir OUT [--weights ckpt.pth] [KEY VALUE ...]
+
+Builds MODEL.META_ARCHITECTURE through the registry from the yaml (config.load_config), loads the weights with the reference's
+key conversions (checkpoint.load_checkpoint; every tensor of the evaluated network must load), and runs every video of the
+split through `model([inputs])` with the test loader (data/test_loader.py) and YTVISEvaluator.process.  Predictions stay on the
+device until they are COCO RLE (the meta-arch's inference_rle switch); labels map to the GT file's category ids in sorted order, as
+the registered dataset's metadata maps them.  Writes OUT/results.json (the reference layout),
+OUT/metrics.json (the "segm" dict; not for a split without annotations) and prints one JSON timing line: videos/s, frames/s and
+the fraction of the wall time the model waited on the loader.  Under torch.distributed.run the videos are split round-robin by
+rank and rank 0 writes the files."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description="YTVIS eval-only run of a checkpoint (mask AP / AR, results.json)")
+    ap.add_argument("--config-file", required=True)
+    ap.add_argument("--gt", required=True, help="YTVIS annotation JSON of the split")
+    ap.add_argument("--image-root", required=True, help="directory the JSON's file_names are relative to")
+    ap.add_argument("--output-dir", required=True)
+    ap.add_argument("--weights", default=None, help="torch .pth (default: MODEL.WEIGHTS)")
+    ap.add_argument("--threads", type=int, default=8, help="JPEG decode threads (<= 16)")
+    ap.add_argument("--prefetch", type=int, default=2, help="videos decoded ahead (1 or 2)")
+    ap.add_argument("--dist-backend", default="gloo", help="process group backend under torch.distributed.run")
+    ap.add_argument("opts", nargs=argparse.REMAINDER, help="config overrides KEY VALUE ...")
+    return ap.parse_args(argv)
+
+
+def build_model(cfg, weights, device):
+    from .checkpoint import evaluated_prefixes, load_checkpoint
+    from .modeling.meta_arch import META_ARCH_REGISTRY
+    model = META_ARCH_REGISTRY.get(cfg.MODEL.META_ARCHITECTURE).from_config(cfg).to(device)
+    if not weights:
+        raise ValueError("no weights: pass --weights or set MODEL.WEIGHTS")
+    info = load_checkpoint(model, weights)
+    pre = evaluated_prefixes(model)
+    missing = [k for k in info["missing"] if k.startswith(pre)]
+    if missing:
+        raise RuntimeError(f"{len(missing)} tensors of the evaluated network were not loaded from {weights}: {missing[:8]}")
+    model.eval()
+    model.inference_rle = True
+    return model
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    from .config import load_config
+    from .data.test_loader import YTVISTestLoader
+    from .ytvis_eval import YTVISEvaluator
+    import torch.distributed as dist
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1 and not dist.is_initialized():
+        dist.init_process_group(a.dist_backend)
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    device = torch.device("cuda", local % torch.cuda.device_count())
+    torch.cuda.set_device(device)
+
+    cfg = load_config(a.config_file, a.opts)
+    model = build_model(cfg, a.weights or cfg.MODEL.WEIGHTS, device)
+    with open(a.gt) as fh:
+        gt_doc = json.load(fh)
+    # labels -> dataset category ids as the registered dataset's metadata maps them (load_ytvis_json: sorted ids, contiguous)
+    id_map = {c: i for i, c in enumerate(sorted(c["id"] for c in gt_doc.get("categories", [])))} or None
+    evaluator = YTVISEvaluator(json_file=gt_doc, distributed=True, output_dir=a.output_dir, dataset_id_to_contiguous_id=id_map)
+    evaluator.reset()
+    loader = YTVISTestLoader.from_config(cfg, gt_doc, a.image_root, device=device, threads=a.threads, prefetch=a.prefetch)
+
+    nvid = nfr = 0
+    torch.cuda.synchronize(device)
+    t0 = time.perf_counter()
+    with torch.no_grad():
+        for inputs in loader:
+            outputs = model([inputs])
+            evaluator.process([inputs], outputs)
+            nvid += 1
+            nfr += len(inputs["image"])
+    torch.cuda.synchronize(device)
+    wall = time.perf_counter() - t0
+
+    results = evaluator.evaluate()
+    if rank == 0:
+        os.makedirs(a.output_dir, exist_ok=True)
+        if "segm" in results:
+            with open(os.path.join(a.output_dir, "metrics.json"), "w") as fh:
+                json.dump(results["segm"], fh)
+    line = {"rank": rank, "videos": nvid, "frames": nfr, "wall_s": round(wall, 4),
+            "videos_per_s": round(nvid / wall, 4) if wall > 0 else None,
+            "frames_per_s": round(nfr / wall, 3) if wall > 0 else None,
+            "loader_wait_fraction": round(loader.wait_s / wall, 4) if wall > 0 else None}
+    print(json.dumps(line), flush=True)
+    if dist.is_initialized():
+        dist.barrier()
+        dist.destroy_process_group()
+    return results
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

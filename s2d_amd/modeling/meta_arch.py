@@ -195,6 +195,7 @@ class KDVideoMaskFormer(nn.Module):
         # they are evaluated at the attention masks' source pixels only; True computes the full maps like the reference.
         self.teacher_aux_masks = False
         self.overlap_teacher, self._side = False, None
+        self.inference_rle = False                  # eval branch: pred_masks as COCO RLE lists encoded on the device (inference_video rle=True)
         self._side_delay_cycles = 0                 # tests only: spin the side stream this many cycles before the GT criterion
 
     @classmethod
@@ -540,17 +541,18 @@ class KDVideoMaskFormer(nn.Module):
         student, TEST.EVAL_STUDENT), then inference_video (:530-610) on the device -> {image_size, pred_scores,
         pred_labels, pred_masks}."""
         net = self.student if self.eval_student else self.teacher
-        return _inference(net, images, batched_inputs, self.num_predictions_inference, self.use_nms, self.nms_threshold)
+        return _inference(net, images, batched_inputs, self.num_predictions_inference, self.use_nms, self.nms_threshold,
+                          rle=getattr(self, "inference_rle", False))
 
 
-def _inference(net, images, batched_inputs, num_predictions, use_nms, nms_threshold):
+def _inference(net, images, batched_inputs, num_predictions, use_nms, nms_threshold, rle=False):
     out = net(images, False)
     video = batched_inputs[0]
     first = video["image"][0]
     image_size = tuple(int(v) for v in first.shape[-2:])            # size without padding (images.image_sizes[0], :349)
     height, width = video.get("height", image_size[0]), video.get("width", image_size[1])   # :351-352
     return inference_video(out.class_logits[-1][0], out.mask_logits[-1][0], (out.T, out.hm, out.wm), tuple(images.shape[1:3]),
-                           image_size, (int(height), int(width)), num_predictions, use_nms, nms_threshold)
+                           image_size, (int(height), int(width)), num_predictions, use_nms, nms_threshold, rle=rle)
 
 
 @META_ARCH_REGISTRY.register()
@@ -565,6 +567,7 @@ class VideoMaskFormer(nn.Module):
         self.use_nms, self.nms_threshold, self.num_predictions = use_nms, nms_threshold, num_predictions
         self.register_buffer("pixel_mean", torch.tensor(pixel_mean, dtype=torch.float32).view(-1, 1, 1), False)
         self.register_buffer("pixel_std", torch.tensor(pixel_std, dtype=torch.float32).view(-1, 1, 1), False)
+        self.inference_rle = False                  # see KDVideoMaskFormer
 
     @classmethod
     def from_config(cls, cfg):  # video_maskformer_model.py:97-187 (the sparse-class / entropy / DropLoss variants are not on the path)
@@ -639,7 +642,8 @@ class VideoMaskFormer(nn.Module):
         if not self.training:                                           # video_maskformer_model.py:241-264
             net = lambda x, training: self.sem_seg_head(self.backbone(x), training)   # noqa: E731
             with torch.no_grad():
-                return _inference(net, images, batched_inputs, self.num_predictions, self.use_nms, self.nms_threshold)
+                return _inference(net, images, batched_inputs, self.num_predictions, self.use_nms, self.nms_threshold,
+                                  rle=getattr(self, "inference_rle", False))
         Hp, Wp = images.shape[1:3]
         gt = TargetSet.from_list(_gt_target_list(batched_inputs, self.num_frames, Hp, Wp, self.device), device=self.device)
         params = [p for p in list(self.backbone.parameters()) + list(self.sem_seg_head.parameters()) if p.requires_grad]

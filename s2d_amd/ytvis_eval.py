@@ -113,6 +113,20 @@ def plane_areas(bits):
     return area
 
 
+def plane_bboxes(bits, H, W):
+    """int32 CUDA bit planes [F, ceil(H*W/32)] -> int32 CUDA [F, 4]: x, y, w, h per plane, pycocotools rleToBbox
+    (mask_util.toBbox) semantics; 0, 0, 0, 0 for an empty plane (s2d_mask_plane_bbox_u32)"""
+    import torch
+    from . import ops
+    from ._lib import lib
+    ops._chk(bits, torch.int32)
+    F, words = bits.shape
+    bbox = torch.empty((F, 4), device=bits.device, dtype=torch.int32)
+    if F:
+        lib().call("s2d_mask_plane_bbox_u32", bits, F, H, W, words, bbox, ops._stream())
+    return bbox
+
+
 def cross_counts(a, b):
     """int32 CUDA tracks a [D, words], b [G, words] -> int64 CUDA [D, G]: sum of popcount(a[d] & b[g])"""
     import torch
