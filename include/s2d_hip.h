@@ -688,6 +688,18 @@ int s2d_aug_warp_frames_u8(const uint8_t *frames, int T, int H0, int W0, void *a
  * pixel (apply_segmentation). */
 int s2d_aug_warp_masks_u8(const uint8_t *masks, int N, int T, int H0, int W0, const void *aug_frames_dev, int H1, int W1, uint8_t *out,
                           hipStream_t stream);
+/* s2d_aug_warp_frames_u8 for frames u8 [T][H0][W0][3] (the layout a JPEG decodes to); out stays u8 [T][3][H1][W1] and is
+ * bit-identical to s2d_aug_warp_frames_u8 on the planar copy.  The crop mean is summed as integers over many workgroups per
+ * frame; the last two words of each record (record floats 14..15) are its scratch: 0 on entry, 0 again on return. */
+int s2d_aug_warp_frames_hwc_u8(const uint8_t *frames, int T, int H0, int W0, void *aug_frames_dev, int H1, int W1, uint8_t *out,
+                               hipStream_t stream);
+/* Annotation masks straight from bit planes bits [P][words_per_plane] (row-major H0 x W0, the s2d_pack_mask_bits_u8 /
+ * s2d_rle_decode_bits layout), in the clip's slot order: plane_of DEVICE int32 [T][S] names the plane of slot s at frame t
+ * (-1: the mapper's dummy slot, an all-zero plane, nothing read; the host guarantees plane_of < P).  out u8 [T][S][H1][W1]
+ * (0 / 1, frame-major), the pixel rule of s2d_aug_warp_masks_u8; area u32 [T][S] = pixels of each output plane (zeroed by the
+ * call).  S == 0 is a no-op. */
+int s2d_aug_warp_mask_bits(const uint32_t *bits, long words_per_plane, const int *plane_of, int S, int T, int H0, int W0,
+                           const void *aug_frames_dev, int H1, int W1, uint8_t *out, unsigned *area, hipStream_t stream);
 
 /* Sparse-mask densification of the trainer (`propagate_sparse_masks`, mask2former_video/engine/train_loop.py:30-156): all output
  * planes of a clip in one launch.  plan_dev: n_planes records {uint64 address of a source plane (bool / u8 [H, W], device memory),

@@ -46,10 +46,23 @@ DEFAULTS = {
         "MAX_SIZE_TEST": 1333, "RANDOM_FLIP": "horizontal", "FORMAT": "BGR",
         "CROP": {"ENABLED": False, "TYPE": "relative_range", "SIZE": [0.9, 0.9]},
         "SAMPLING_FRAME_NUM": 2, "SAMPLING_FRAME_RANGE": 20, "SAMPLING_FRAME_SHUFFLE": False, "AUGMENTATIONS": [],
+        "DENSE_ANNOTATION_SELECTION": True, "DISENTANGLE_DISTILLATION_LOADER": False, "DISTILLATION_DENSE_ANNOTATION_SELECTION": True,
     },
     "DATASETS": {"TRAIN": (), "TEST": ()},
-    "DATALOADER": {"NUM_WORKERS": 4},
-    "SOLVER": {"ACCUM_ITER": 1},
+    "DATALOADER": {"NUM_WORKERS": 4, "ASPECT_RATIO_GROUPING": True, "FILTER_EMPTY_ANNOTATIONS": True, "COPY_PASTE": False,
+                   "COPY_PASTE_RATE": 0.0, "COPY_PASTE_RANDOM_NUM": True, "VISUALIZE_COPY_PASTE": False, "COPY_PASTE_MIN_RATIO": 0.5, "COPY_PASTE_MAX_RATIO": 1.0,
+                   "COPY_PASTE_DENSIFY_SPARSE": False},
+    # the solver keys of detectron2's get_cfg() + add_maskformer2_config that the optimizer, the LR scheduler and the training
+    # driver read
+    "SOLVER": {"ACCUM_ITER": 1, "OPTIMIZER": "ADAMW", "BASE_LR": 0.001, "MAX_ITER": 40000, "STEPS": (30000,),
+               "WEIGHT_DECAY": 0.0001, "WEIGHT_DECAY_NORM": 0.0, "WEIGHT_DECAY_EMBED": 0.0, "BACKBONE_MULTIPLIER": 0.1,
+               "LR_SCHEDULER_NAME": "WarmupMultiStepLR", "GAMMA": 0.1, "WARMUP_FACTOR": 0.001, "WARMUP_ITERS": 1000,
+               "WARMUP_METHOD": "linear", "POLY_LR_POWER": 0.9, "POLY_LR_CONSTANT_ENDING": 0.0, "CHECKPOINT_PERIOD": 5000,
+               "IMS_PER_BATCH": 16,
+               "CLIP_GRADIENTS": {"ENABLED": False, "CLIP_TYPE": "value", "CLIP_VALUE": 1.0, "NORM_TYPE": 2.0},
+               "AMP": {"ENABLED": False}},
+    "TEST": {"EVAL_PERIOD": 0},
+    "SEED": -1,
     "OUTPUT_DIR": "./output",
 }
 

@@ -20,7 +20,26 @@ struct AugFrame {
     float bright;      // RandomBrightness: img * w                      (1 = off)
     float contrast;    // RandomContrast:  (1 - w) * mean + w * img      (1 = off)
     float cmean;       // the mean the contrast blend pulls towards (filled by aug_crop_mean_kernel when < 0)
-    float pad0, pad1, pad2;
+    float pad0;
+    unsigned long long csum;   // 0 on entry and exit; the HWC crop mean's integer accumulator in between
+};
+
+// Output pixel (x, y) -> its source point (sx, sy); true iff the point lies inside the crop rectangle.  Every kernel that reads
+// under the map calls this one function, so the frame, mask and bit-plane kernels agree on the point to the last bit.
+__device__ __forceinline__ bool aug_source_point(const AugFrame &f, int x, int y, float &sx, float &sy)
+{
+    const float px = x + 0.5f, py = y + 0.5f;
+    sx = f.a11 * px + f.a12 * py + f.a13;
+    sy = f.a21 * px + f.a22 * py + f.a23;
+    return sx >= f.cx && sy >= f.cy && sx < f.cx + f.cw && sy < f.cy + f.ch;
+}
+
+// Source frame layouts: [T][3][H0][W0] (planar) and [T][H0][W0][3] (what a JPEG decodes to)
+struct SrcCHW {
+    __device__ static long at(int t, int c, long y, long x, int H0, int W0) { return ((long)t * 3 + c) * H0 * W0 + y * W0 + x; }
+};
+struct SrcHWC {
+    __device__ static long at(int t, int c, long y, long x, int H0, int W0) { return (((long)t * H0 + y) * W0 + x) * 3 + c; }
 };
 
 __global__ __launch_bounds__(256) void aug_crop_mean_kernel(const uint8_t *__restrict__ src, int H0, int W0, AugFrame *__restrict__ fr)
@@ -47,16 +66,16 @@ __global__ __launch_bounds__(256) void aug_crop_mean_kernel(const uint8_t *__res
 
 __device__ __forceinline__ float trunc_u8(float v) { return truncf(fminf(fmaxf(v, 0.f), 255.f)); }
 
+template <class L>
 __global__ __launch_bounds__(256) void aug_warp_frames_kernel(const uint8_t *__restrict__ src, int H0, int W0, const AugFrame *__restrict__ fr,
                                                               int H1, int W1, uint8_t *__restrict__ out)
 {
     const int t = blockIdx.z, y = blockIdx.y, x = blockIdx.x * 256 + threadIdx.x;
     if (x >= W1) return;
     const AugFrame f = fr[t];
-    const float px = x + 0.5f, py = y + 0.5f;
-    const float sx = f.a11 * px + f.a12 * py + f.a13, sy = f.a21 * px + f.a22 * py + f.a23;
+    float sx, sy;
     uint8_t r[3] = {0, 0, 0};
-    if (sx >= f.cx && sy >= f.cy && sx < f.cx + f.cw && sy < f.cy + f.ch) {
+    if (aug_source_point(f, x, y, sx, sy)) {
         const float fx = sx - 0.5f, fy = sy - 0.5f;
         const float x0f = floorf(fx), y0f = floorf(fy);
         const float lx = fx - x0f, ly = fy - y0f;
@@ -65,9 +84,8 @@ __global__ __launch_bounds__(256) void aug_warp_frames_kernel(const uint8_t *__r
         const int y0 = min(max((int)y0f, yl), yh), y1 = min(max((int)y0f + 1, yl), yh);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const uint8_t *p = src + ((long)t * 3 + c) * H0 * W0;
-            const float v = (1.f - ly) * ((1.f - lx) * p[(long)y0 * W0 + x0] + lx * p[(long)y0 * W0 + x1]) +
-                            ly * ((1.f - lx) * p[(long)y1 * W0 + x0] + lx * p[(long)y1 * W0 + x1]);
+            const float v = (1.f - ly) * ((1.f - lx) * src[L::at(t, c, y0, x0, H0, W0)] + lx * src[L::at(t, c, y0, x1, H0, W0)]) +
+                            ly * ((1.f - lx) * src[L::at(t, c, y1, x0, H0, W0)] + lx * src[L::at(t, c, y1, x1, H0, W0)]);
             float q = rintf(v);                                               // the resampled uint8 image
             if (f.bright != 1.f) q = trunc_u8(f.bright * q);                  // BlendTransform: clip, astype(uint8)
             if (f.contrast != 1.f) q = trunc_u8((1.f - f.contrast) * f.cmean + f.contrast * q);
@@ -78,6 +96,45 @@ __global__ __launch_bounds__(256) void aug_warp_frames_kernel(const uint8_t *__r
     for (int c = 0; c < 3; ++c) out[(((long)t * 3 + c) * H1 + y) * W1 + x] = r[c];
 }
 
+// The crop mean of [T][H0][W0][3] frames, spread over gridDim.x workgroups per frame: each sums whole crop rows as integers and
+// adds its partial to the frame's csum (exact, so the order does not matter); aug_crop_mean_finish_kernel turns the sum into the
+// same float aug_crop_mean_kernel computes from the same (exact) double.  Frames whose cmean is given (>= 0) are skipped.
+__global__ __launch_bounds__(256) void aug_crop_sum_hwc_kernel(const uint8_t *__restrict__ src, int H0, int W0, AugFrame *__restrict__ fr)
+{
+    __shared__ unsigned long long part[256];
+    const int t = blockIdx.y;
+    const AugFrame f = fr[t];
+    if (!(f.cmean < 0.f)) return;                                          // uniform over the workgroup
+    const int x0 = (int)f.cx, y0 = (int)f.cy, w = (int)f.cw, h = (int)f.ch;
+    const long row = 3L * w;
+    unsigned long long s = 0;
+    for (int r = blockIdx.x; r < h; r += gridDim.x) {
+        const uint8_t *p = src + SrcHWC::at(t, 0, y0 + r, x0, H0, W0);
+        for (long i = threadIdx.x; i < row; i += 256) s += p[i];
+    }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && part[0]) atomicAdd(&fr[t].csum, part[0]);
+}
+
+__global__ void aug_crop_sum_reset_kernel(AugFrame *__restrict__ fr, int T)
+{
+    for (int t = threadIdx.x; t < T; t += blockDim.x) fr[t].csum = 0ull;
+}
+
+__global__ void aug_crop_mean_finish_kernel(AugFrame *__restrict__ fr, int T)
+{
+    for (int t = threadIdx.x; t < T; t += blockDim.x) {
+        const AugFrame f = fr[t];
+        if (f.cmean < 0.f) fr[t].cmean = (float)((double)f.csum / (3.0 * (int)f.cw * (int)f.ch)) * f.bright;
+        fr[t].csum = 0ull;
+    }
+}
+
 // masks [N][T][H0][W0] (0 / non-0) -> [N][T][H1][W1] (0 / 1): nearest source pixel under the same map (apply_segmentation)
 __global__ __launch_bounds__(256) void aug_warp_masks_kernel(const uint8_t *__restrict__ src, int T, int H0, int W0,
                                                              const AugFrame *__restrict__ fr, int H1, int W1, uint8_t *__restrict__ out)
@@ -85,12 +142,66 @@ __global__ __launch_bounds__(256) void aug_warp_masks_kernel(const uint8_t *__re
     const int nt = blockIdx.z, t = nt % T, y = blockIdx.y, x = blockIdx.x * 256 + threadIdx.x;
     if (x >= W1) return;
     const AugFrame f = fr[t];
-    const float px = x + 0.5f, py = y + 0.5f;
-    const float sx = f.a11 * px + f.a12 * py + f.a13, sy = f.a21 * px + f.a22 * py + f.a23;
+    float sx, sy;
     uint8_t r = 0;
-    if (sx >= f.cx && sy >= f.cy && sx < f.cx + f.cw && sy < f.cy + f.ch)
+    if (aug_source_point(f, x, y, sx, sy))
         r = src[((long)nt * H0 + (int)floorf(sy)) * W0 + (int)floorf(sx)] != 0;
     out[((long)nt * H1 + y) * W1 + x] = r;
+}
+
+// Annotation bit planes (row-major, 32 pixels per word: the s2d_pack_mask_bits_u8 / s2d_rle_decode_bits layout) -> the clip's
+// frame-major u8 masks [T][S][H1][W1] with the nearest-tap rule of aug_warp_masks_kernel, plus each output plane's pixel count.
+// Block z = t * S + s; plane_of[z] < 0 is a dummy slot: an all-zero plane that reads nothing.  The output plane is walked as one
+// flat row of H1 * W1 bytes, MB_PIX consecutive bytes per lane (a lane's bytes may straddle two image rows), so no lane idles at
+// the end of an image row and the 4-byte store applies whatever W1 is, wherever the address is 4-aligned.  Counts: one ballot +
+// popcount per byte position, one atomic per wave.
+constexpr int MB_PIX = 4;
+
+__global__ __launch_bounds__(256) void aug_warp_mask_bits_kernel(const uint32_t *__restrict__ bits, long wpp, const int *__restrict__ plane_of,
+                                                                 int S, int H0, int W0, const AugFrame *__restrict__ fr, int H1, int W1,
+                                                                 uint8_t *__restrict__ out, unsigned *__restrict__ area)
+{
+    const int z = blockIdx.y, t = z / S;
+    const long npix = (long)H1 * W1;
+    const long i0 = ((long)blockIdx.x * 256 + threadIdx.x) * MB_PIX;
+    const int p = plane_of[z];
+    unsigned v = 0;                                                   // byte e: flat output pixel i0 + e
+    if (p >= 0 && i0 < npix) {
+        const AugFrame f = fr[t];
+        const uint32_t *pl = bits + (long)p * wpp;
+        int y = (int)(i0 / W1), x = (int)(i0 - (long)y * W1);
+        long src[MB_PIX];                                             // source bit index of each byte, -1: outside the crop
+#pragma unroll
+        for (int e = 0; e < MB_PIX; ++e) {
+            float sx, sy;
+            src[e] = -1;
+            if (i0 + e < npix && aug_source_point(f, x, y, sx, sy)) {
+                const int iy = min(max((int)floorf(sy), 0), H0 - 1), ix = min(max((int)floorf(sx), 0), W0 - 1);
+                src[e] = (long)iy * W0 + ix;
+            }
+            if (++x == W1) { x = 0; ++y; }
+        }
+        uint32_t w[MB_PIX];                                           // all taps in flight before the first is used
+#pragma unroll
+        for (int e = 0; e < MB_PIX; ++e) w[e] = pl[src[e] < 0 ? 0 : src[e] >> 5];
+#pragma unroll
+        for (int e = 0; e < MB_PIX; ++e)
+            if (src[e] >= 0) v |= ((w[e] >> (src[e] & 31)) & 1u) << (8 * e);
+    }
+    if (i0 < npix) {
+        uint8_t *o = out + (long)z * npix + i0;
+        if (i0 + MB_PIX <= npix && (reinterpret_cast<uintptr_t>(o) & (MB_PIX - 1)) == 0) {
+            *reinterpret_cast<unsigned *>(o) = v;
+        } else {
+#pragma unroll
+            for (int e = 0; e < MB_PIX; ++e)
+                if (i0 + e < npix) o[e] = (uint8_t)(v >> (8 * e));
+        }
+    }
+    int n = 0;
+#pragma unroll
+    for (int e = 0; e < MB_PIX; ++e) n += __popcll(__ballot((v >> (8 * e)) & 1u));
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(area + z, (unsigned)n);
 }
 
 // ---- video copy-paste (engine/train_loop.py:441-560) ---------------------------------------------------------------
@@ -313,7 +424,21 @@ int s2d_aug_warp_frames_u8(const uint8_t *frames, int T, int H0, int W0, void *a
     if (T <= 0 || H0 <= 0 || W0 <= 0 || H1 <= 0 || W1 <= 0 || H1 > 65535) return S2D_ERR_ARG;
     AugFrame *fr = reinterpret_cast<AugFrame *>(aug_frames_dev);
     hipLaunchKernelGGL(aug_crop_mean_kernel, dim3(T), dim3(256), 0, stream, frames, H0, W0, fr);
-    hipLaunchKernelGGL(aug_warp_frames_kernel, dim3(cdiv(W1, 256), H1, T), dim3(256), 0, stream, frames, H0, W0, fr, H1, W1, out);
+    hipLaunchKernelGGL(aug_warp_frames_kernel<SrcCHW>, dim3(cdiv(W1, 256), H1, T), dim3(256), 0, stream, frames, H0, W0, fr, H1, W1, out);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_aug_warp_frames_hwc_u8(const uint8_t *frames, int T, int H0, int W0, void *aug_frames_dev, int H1, int W1, uint8_t *out,
+                               hipStream_t stream)
+{
+    if (T <= 0 || H0 <= 0 || W0 <= 0 || H1 <= 0 || W1 <= 0 || H1 > 65535 || T > 65535) return S2D_ERR_ARG;
+    AugFrame *fr = reinterpret_cast<AugFrame *>(aug_frames_dev);
+    const int g = H0 < 128 ? H0 : 128;                                // workgroups per frame for the crop sum: a few crop rows each
+    hipLaunchKernelGGL(aug_crop_sum_reset_kernel, dim3(1), dim3(256), 0, stream, fr, T);
+    hipLaunchKernelGGL(aug_crop_sum_hwc_kernel, dim3(g, T), dim3(256), 0, stream, frames, H0, W0, fr);
+    hipLaunchKernelGGL(aug_crop_mean_finish_kernel, dim3(1), dim3(256), 0, stream, fr, T);
+    hipLaunchKernelGGL(aug_warp_frames_kernel<SrcHWC>, dim3(cdiv(W1, 256), H1, T), dim3(256), 0, stream, frames, H0, W0, fr, H1, W1, out);
     S2D_CHECK_LAUNCH();
     return S2D_OK;
 }
@@ -325,6 +450,20 @@ int s2d_aug_warp_masks_u8(const uint8_t *masks, int N, int T, int H0, int W0, co
     if (N == 0) return S2D_OK;
     hipLaunchKernelGGL(aug_warp_masks_kernel, dim3(cdiv(W1, 256), H1, N * T), dim3(256), 0, stream, masks, T, H0, W0,
                        reinterpret_cast<const AugFrame *>(aug_frames_dev), H1, W1, out);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_aug_warp_mask_bits(const uint32_t *bits, long words_per_plane, const int *plane_of, int S, int T, int H0, int W0,
+                           const void *aug_frames_dev, int H1, int W1, uint8_t *out, unsigned *area, hipStream_t stream)
+{
+    if (S < 0 || T <= 0 || H0 <= 0 || W0 <= 0 || H1 <= 0 || W1 <= 0 || H1 > 65535 || (long)S * T > 65535 ||
+        words_per_plane < ((long)H0 * W0 + 31) / 32)
+        return S2D_ERR_ARG;
+    if (S == 0) return S2D_OK;
+    if (s2d_zero_async(area, sizeof(unsigned) * (size_t)S * T, stream) != S2D_OK) return S2D_ERR_LAUNCH;
+    hipLaunchKernelGGL(aug_warp_mask_bits_kernel, dim3(cdiv((long)H1 * W1, 256 * MB_PIX), S * T), dim3(256), 0, stream, bits,
+                       words_per_plane, plane_of, S, H0, W0, reinterpret_cast<const AugFrame *>(aug_frames_dev), H1, W1, out, area);
     S2D_CHECK_LAUNCH();
     return S2D_OK;
 }

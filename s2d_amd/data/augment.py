@@ -106,3 +106,37 @@ def augment_clip(frames_u8, masks_u8, params, out_hw):
         mo = torch.empty((N, T, H1, W1), device=frames_u8.device, dtype=torch.uint8)
         lib().call("s2d_aug_warp_masks_u8", masks_u8.contiguous(), N, T, H0, W0, p, H1, W1, mo, _stream())
     return out, mo
+
+
+def augment_frames_hwc(frames_hwc, params_dev, out_hw):
+    """frames u8 CUDA [T,H0,W0,3] (as decoded), params float32 CUDA [T,16] -> u8 [T,3,H1,W1]: s2d_aug_warp_frames_hwc_u8,
+    bit-identical to augment_clip on the planar frames.  params_dev gets its cmean filled in (as s2d_aug_warp_frames_u8 does)."""
+    T, H0, W0, C = frames_hwc.shape
+    if C != 3 or frames_hwc.dtype != torch.uint8 or not frames_hwc.is_contiguous():
+        raise ValueError("frames must be contiguous uint8 [T, H0, W0, 3]")
+    if params_dev.shape != (T, 16) or params_dev.dtype != torch.float32 or not params_dev.is_contiguous():
+        raise ValueError("params must be contiguous float32 [T, 16] on the device")
+    H1, W1 = out_hw
+    out = torch.empty((T, 3, H1, W1), device=frames_hwc.device, dtype=torch.uint8)
+    lib().call("s2d_aug_warp_frames_hwc_u8", frames_hwc, T, H0, W0, params_dev, H1, W1, out, _stream())
+    return out
+
+
+def warp_mask_bits(bits, plane_of, H0, W0, params_dev, out_hw):
+    """bits int32 CUDA [P, ceil(H0*W0/32)] (ytvis_eval.decode_frames planes), plane_of host int [T, S] (-1: dummy slot)
+    -> (masks u8 [T,S,H1,W1] in {0, 1}, pixel counts int32 CUDA [T,S]): s2d_aug_warp_mask_bits.  plane_of goes up from pinned
+    memory without blocking, so the call can run on a side stream."""
+    P, wpp = bits.shape
+    if wpp < (H0 * W0 + 31) // 32 or bits.dtype != torch.int32 or not bits.is_contiguous():
+        raise ValueError("bits must be contiguous int32 [P, ceil(H0*W0/32)]")
+    po = np.asarray(plane_of, np.int64)
+    if po.ndim != 2 or (po.size and (po.max() >= P or po.min() < -1)):
+        raise ValueError(f"plane_of must be [T, S] with entries in [-1, {P})")
+    T, S = po.shape
+    H1, W1 = out_hw
+    dev = bits.device
+    out = torch.empty((T, S, H1, W1), device=dev, dtype=torch.uint8)
+    area = torch.empty((T, S), device=dev, dtype=torch.int32)               # zeroed by the call
+    po_d = torch.from_numpy(np.ascontiguousarray(po, np.int32)).pin_memory().to(dev, non_blocking=True) if S else None
+    lib().call("s2d_aug_warp_mask_bits", bits, wpp, po_d, S, T, H0, W0, params_dev, H1, W1, out, area, _stream())
+    return out, area

@@ -49,16 +49,62 @@ def build_model(cfg, weights, device):
     return model
 
 
+def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, prefetch=2):
+    """score `model` on a YTVIS split: every video through `model([inputs])` (eval mode, predictions as COCO RLE) with the test
+    loader and YTVISEvaluator; writes output_dir/results.json and, on rank 0 of a split with annotations, output_dir/metrics.json.
+    The model's training mode and inference_rle switch are restored afterwards.  -> (results, timing line dict)"""
+    from .data.test_loader import YTVISTestLoader
+    from .ytvis_eval import YTVISEvaluator
+    import torch.distributed as dist
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    if isinstance(gt, str):
+        with open(gt) as fh:
+            gt = json.load(fh)
+    # labels -> dataset category ids as the registered dataset's metadata maps them (load_ytvis_json: sorted ids, contiguous)
+    id_map = {c: i for i, c in enumerate(sorted(c["id"] for c in gt.get("categories", [])))} or None
+    evaluator = YTVISEvaluator(json_file=gt, distributed=True, output_dir=output_dir, dataset_id_to_contiguous_id=id_map)
+    evaluator.reset()
+    loader = YTVISTestLoader.from_config(cfg, gt, image_root, device=device, threads=threads, prefetch=prefetch)
+
+    was_training, was_rle = model.training, getattr(model, "inference_rle", False)
+    model.eval()
+    model.inference_rle = True
+    nvid = nfr = 0
+    try:
+        torch.cuda.synchronize(device)
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            for inputs in loader:
+                outputs = model([inputs])
+                evaluator.process([inputs], outputs)
+                nvid += 1
+                nfr += len(inputs["image"])
+        torch.cuda.synchronize(device)
+        wall = time.perf_counter() - t0
+    finally:
+        model.train(was_training)
+        model.inference_rle = was_rle
+
+    results = evaluator.evaluate()
+    if rank == 0:
+        os.makedirs(output_dir, exist_ok=True)
+        if "segm" in results:
+            with open(os.path.join(output_dir, "metrics.json"), "w") as fh:
+                json.dump(results["segm"], fh)
+    line = {"rank": rank, "videos": nvid, "frames": nfr, "wall_s": round(wall, 4),
+            "videos_per_s": round(nvid / wall, 4) if wall > 0 else None,
+            "frames_per_s": round(nfr / wall, 3) if wall > 0 else None,
+            "loader_wait_fraction": round(loader.wait_s / wall, 4) if wall > 0 else None}
+    return results, line
+
+
 def main(argv=None):
     a = parse_args(argv)
     from .config import load_config
-    from .data.test_loader import YTVISTestLoader
-    from .ytvis_eval import YTVISEvaluator
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 and not dist.is_initialized():
         dist.init_process_group(a.dist_backend)
-    rank = dist.get_rank() if dist.is_initialized() else 0
     local = int(os.environ.get("LOCAL_RANK", "0"))
     device = torch.device("cuda", local % torch.cuda.device_count())
     torch.cuda.set_device(device)
@@ -67,34 +113,7 @@ def main(argv=None):
     model = build_model(cfg, a.weights or cfg.MODEL.WEIGHTS, device)
     with open(a.gt) as fh:
         gt_doc = json.load(fh)
-    # labels -> dataset category ids as the registered dataset's metadata maps them (load_ytvis_json: sorted ids, contiguous)
-    id_map = {c: i for i, c in enumerate(sorted(c["id"] for c in gt_doc.get("categories", [])))} or None
-    evaluator = YTVISEvaluator(json_file=gt_doc, distributed=True, output_dir=a.output_dir, dataset_id_to_contiguous_id=id_map)
-    evaluator.reset()
-    loader = YTVISTestLoader.from_config(cfg, gt_doc, a.image_root, device=device, threads=a.threads, prefetch=a.prefetch)
-
-    nvid = nfr = 0
-    torch.cuda.synchronize(device)
-    t0 = time.perf_counter()
-    with torch.no_grad():
-        for inputs in loader:
-            outputs = model([inputs])
-            evaluator.process([inputs], outputs)
-            nvid += 1
-            nfr += len(inputs["image"])
-    torch.cuda.synchronize(device)
-    wall = time.perf_counter() - t0
-
-    results = evaluator.evaluate()
-    if rank == 0:
-        os.makedirs(a.output_dir, exist_ok=True)
-        if "segm" in results:
-            with open(os.path.join(a.output_dir, "metrics.json"), "w") as fh:
-                json.dump(results["segm"], fh)
-    line = {"rank": rank, "videos": nvid, "frames": nfr, "wall_s": round(wall, 4),
-            "videos_per_s": round(nvid / wall, 4) if wall > 0 else None,
-            "frames_per_s": round(nfr / wall, 3) if wall > 0 else None,
-            "loader_wait_fraction": round(loader.wait_s / wall, 4) if wall > 0 else None}
+    results, line = evaluate_model(cfg, model, gt_doc, a.image_root, a.output_dir, device, a.threads, a.prefetch)
     print(json.dumps(line), flush=True)
     if dist.is_initialized():
         dist.barrier()

@@ -6,10 +6,12 @@ nn.Sequential(backbone, head) so checkpoint keys are student.0.* / student.1.*; 
 .device).  The forward is the measured hot path: normalise/pad -> student -> teacher -> GT criterion -> KD targets ->
 KD criterion -> rename/weight, all enqueued on the current stream without a host synchronisation.
 """
+import numpy as np
 import torch
 from torch import nn
 
 from .. import ops
+from .._lib import lib
 from .backbone import ResNet50
 from .criterion import TargetSet, VideoHungarianMatcher, VideoSetCriterion
 from .pixel_decoder import MSDeformAttnPixelDecoder
@@ -137,6 +139,26 @@ def _frames_to_device(batched_inputs, device):
     return x.to(device=device, dtype=torch.uint8, non_blocking=True).contiguous()
 
 
+def _normalize_batch(batched_inputs, device, div, mean, std):
+    """frames of the batch -> normalised, zero-padded f32 [F,Hp,Wp,4].  Clips of different sizes (a training batch of the
+    loader) are padded to the largest, rounded up to `div`, as ImageList.from_tensors pads them (0 after normalisation)."""
+    sizes = {tuple(f.shape[-2:]) for video in batched_inputs for f in video["image"]}
+    if len(sizes) == 1:
+        return ops.normalize_pad(_frames_to_device(batched_inputs, device), div, mean, std)
+    Hp = (max(h for h, _ in sizes) + div - 1) // div * div
+    Wp = (max(w for _, w in sizes) + div - 1) // div * div
+    F = sum(len(video["image"]) for video in batched_inputs)
+    out = torch.empty((F, Hp, Wp, 4), device=device, dtype=torch.float32)
+    f0 = 0
+    for video in batched_inputs:
+        x = _frames_to_device([video], device)
+        n, _, h, w = x.shape
+        lib().call("s2d_normalize_pad_nhwc4_f32", x, n, h, w, Hp, Wp, np.ascontiguousarray(mean, np.float32),
+                       np.ascontiguousarray(std, np.float32), out[f0:f0 + n], ops._stream())
+        f0 += n
+    return out
+
+
 def _gt_target_list(batched_inputs, num_frames, Hp, Wp, device):
     """prepare_targets (kd_video_maskformer_model.py:358-386): paste per-frame BitMasks into [N,T,Hp,Wp], drop
     instances whose ids are -1 in every frame.  Accepts detectron2 Instances (gt_masks.tensor / gt_ids) or plain
@@ -232,9 +254,8 @@ class KDVideoMaskFormer(nn.Module):
         return self.pixel_mean.device
 
     def preprocess(self, batched_inputs):
-        frames = _frames_to_device(batched_inputs, self.device)
-        return ops.normalize_pad(frames, self.size_divisibility, self.pixel_mean.flatten().cpu().numpy(),
-                                 self.pixel_std.flatten().cpu().numpy())
+        return _normalize_batch(batched_inputs, self.device, self.size_divisibility, self.pixel_mean.flatten().cpu().numpy(),
+                                self.pixel_std.flatten().cpu().numpy())
 
     def _kd_nms(self, tgt, cnt, ne, kept=None):
         """the optional mask-NMS of prepare_distillation_targets (kd_video_maskformer_model.py:484-520): greedy over the

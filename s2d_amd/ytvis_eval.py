@@ -47,19 +47,11 @@ def _frame_kind(seg):
 
 
 # --------------------------------------------------------------------------------------------------------------- device
-def decode_frames(segs, H, W, device=None):
-    """COCO RLE frames (compressed dicts, uncompressed dicts, or None for an absent frame), all of size [H, W] -> int32 CUDA
-    bit planes [F, ceil(H*W/32)] (row-major flat index i -> word i/32, bit i%32).  Strings are parsed and every plane decoded
-    on the device (s2d_rle_parse_strings, s2d_rle_decode_bits); uncompressed counts only get their running sums here."""
-    import torch
-    from . import ops
-    from ._lib import lib
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+def stage_rle(segs, H, W):
+    """the host staging of decode_frames: COCO RLE frames (compressed dicts, uncompressed dicts, or None) of size [H, W] ->
+    (chars u8, str_off int64 [F+1], ends int32, nrun int32 [F]) as numpy arrays, the inputs of s2d_rle_parse_strings /
+    s2d_rle_decode_bits.  Uncompressed counts only get their running sums here; compressed strings are parsed on the device."""
     F, hw = len(segs), H * W
-    wpf = (hw + 31) // 32
-    bits = torch.empty((F, wpf), device=dev, dtype=torch.int32)
-    if F == 0:
-        return bits
     lens = np.zeros(F, np.int64)
     nrun = np.zeros(F, np.int32)
     chunks, unc = [], {}
@@ -90,14 +82,35 @@ def decode_frames(segs, H, W, device=None):
     ends_h = np.zeros(total, np.int32)
     for f, e in unc.items():
         ends_h[str_off[f]:str_off[f] + len(e)] = e
-    chars_d = torch.from_numpy(chars).to(dev)
-    off_d = torch.from_numpy(str_off).to(dev)
-    ends_d = torch.from_numpy(ends_h).to(dev)
-    nrun_d = torch.from_numpy(nrun).to(dev)
+    return chars, str_off, ends_h, nrun
+
+
+def decode_staged(staged, H, W, dev, pinned=False):
+    """stage_rle's arrays -> int32 CUDA bit planes [F, ceil(H*W/32)] on the current stream.  pinned: the copies go up from
+    pinned memory without blocking the host (a loader's side stream)"""
+    import torch
+    from . import ops
+    from ._lib import lib
+    chars, str_off, ends_h, nrun = staged
+    F = len(nrun)
+    bits = torch.empty((F, (H * W + 31) // 32), device=dev, dtype=torch.int32)
+    if F == 0:
+        return bits
+    up = (lambda a: torch.from_numpy(a).pin_memory().to(dev, non_blocking=True)) if pinned else (lambda a: torch.from_numpy(a).to(dev))
+    chars_d, off_d, ends_d, nrun_d = up(chars), up(str_off), up(ends_h), up(nrun)
     st = ops._stream()
-    lib().call("s2d_rle_parse_strings", chars_d, off_d, F, hw, ends_d, nrun_d, st)
+    lib().call("s2d_rle_parse_strings", chars_d, off_d, F, H * W, ends_d, nrun_d, st)
     lib().call("s2d_rle_decode_bits", ends_d, off_d, nrun_d, F, H, W, bits, st)
     return bits
+
+
+def decode_frames(segs, H, W, device=None):
+    """COCO RLE frames (compressed dicts, uncompressed dicts, or None for an absent frame), all of size [H, W] -> int32 CUDA
+    bit planes [F, ceil(H*W/32)] (row-major flat index i -> word i/32, bit i%32).  Strings are parsed and every plane decoded
+    on the device (s2d_rle_parse_strings, s2d_rle_decode_bits); uncompressed counts only get their running sums here."""
+    import torch
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    return decode_staged(stage_rle(segs, H, W), H, W, dev)
 
 
 def plane_areas(bits):
