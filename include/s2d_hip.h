@@ -633,6 +633,17 @@ int s2d_tracks_to_masks_u8(const float *tracks, int T, int Np, int H, int W, uin
 int s2d_point_id_counts(const uint8_t *point_masks, const int64_t *idmap, int T, int H, int W, int Hi, int Wi, int max_id,
                         int *counts, int *total, hipStream_t stream);
 
+/* s2d_tracks_to_masks_u8 + s2d_point_id_counts in one launch without the [T][H][W] point mask: tracks f32 [T][P][2] (x,y px) in a
+ * frame of H x W, idmap int64 [T][Hi][Wi] -> the same counts int32 [T][max_id+1] and total int32 [T], bit for bit, for every finite
+ * input.  One workgroup per frame: each point is rounded half to even and bounds-tested as s2d_tracks_to_masks_u8 does, points
+ * with a non-finite coordinate are dropped, the frame's pixel keys are sorted in LDS and each distinct pixel is counted once
+ * (two tracks on one pixel count once, as in the scattered mask), through the nearest rule of s2d_point_id_counts.
+ * Limits: P <= 32768 (the LDS sort: 4 B per key, padded to a power of two, beside 4 (max_id + 2) B of histogram within the
+ * 160 KiB of one CU), max_id <= 8190, H and W < 2^24; anything else returns S2D_ERR_ARG (callers with more points use the
+ * two-launch path). */
+int s2d_track_point_id_counts(const float *tracks, int T, int P, int H, int W, const int64_t *idmap, int Hi, int Wi, int max_id,
+                              int *counts, int *total, hipStream_t stream);
+
 /* get_segmentation_mask (keymask_ident/keymask_utils.py:37-67 == cotracker_matching.py:176-209) for a list of K (frame, object)
  * candidates: out u8 [K][H][W] = (idmap[frames[k]] == objs[k]) * 255, objs[k] == -1 selecting every non-background id.  frames /
  * objs are DEVICE int32 arrays (frame indices are not range-checked here: the caller built them from the same id map).  The

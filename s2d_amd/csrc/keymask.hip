@@ -7,6 +7,8 @@
 //                                                             nearest-resize index map at the point pixels only
 //  K5 point/mask "IoU"      :640-662                          #(points & obj) / #points  -> integer counts per (frame, id)
 //  K6 match loop            :665-719                          one launch for all frames x all object ids of a tracked mask
+//  K3+K5 fused              :453-503 + :640-662               tracks -> per-frame sorted unique point pixels -> id histogram,
+//                                                             no [T,H,W] point mask (s2d_track_point_id_counts)
 //  K1 local correlation     co-tracker (third party, not in the reference tree): self-defined restatement of its local
 //                           4-D correlation: per (frame, track point) the (2r+1)^2 bilinear-sampled neighbourhood
 //                           features dotted with the track's (2r+1)^2 support features.  PARITY UNPINNED.
@@ -54,6 +56,66 @@ __global__ __launch_bounds__(256) void point_id_hist_kernel(const uint8_t *__res
     for (int i = threadIdx.x; i <= max_id; i += 256)
         if (hist[i]) atomicAdd(&counts[(long)t * (max_id + 1) + i], hist[i]);
     if (threadIdx.x == 0 && hist[max_id + 1]) atomicAdd(&total[t], hist[max_id + 1]);
+}
+
+// K3+K5 fused: one workgroup per frame.  The frame's P tracks become pixel keys y*W+x (rounded and bounds-tested exactly as
+// scatter_tracks_kernel; a non-finite or out-of-frame point becomes the sentinel 0xFFFFFFFF), the keys are bitonic-sorted in LDS
+// and each distinct key is looked up in the id map once -- two tracks on one pixel count once, as in the scattered u8 mask.
+// LDS: keys[cap] (cap = power of two >= P) then hist[max_id + 2] (ids 0..max_id, last = total).  Each workgroup owns its
+// rows of counts / total, so nothing is pre-zeroed.
+constexpr unsigned int TRACK_KEY_NONE = 0xFFFFFFFFu;
+constexpr int TRACK_MAX_POINTS = 32768;               // 128 KiB of keys + 32 KiB of histogram (max_id 8190) = 160 KiB of LDS
+
+__global__ __launch_bounds__(1024) void track_point_id_counts_kernel(const float *__restrict__ tracks, int P, int cap, int H, int W,
+                                                                     const int64_t *__restrict__ ids, int Hi, int Wi, int max_id,
+                                                                     int *__restrict__ counts, int *__restrict__ total)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned int track_lds[];
+    unsigned int *keys = track_lds;
+    int *hist = reinterpret_cast<int *>(track_lds + cap);
+    const int t = blockIdx.x;
+    const float *tr = tracks + (long)t * P * 2;
+    for (int i = threadIdx.x; i < cap; i += 1024) {
+        unsigned int k = TRACK_KEY_NONE;
+        if (i < P) {
+            const float fx = tr[2 * i], fy = tr[2 * i + 1];
+            if (isfinite(fx) && isfinite(fy)) {
+                const float x = rintf(fx), y = rintf(fy);          // torch.round: half to even
+                // integer-valued floats against exact float bounds (W, H < 2^24): the same test as the long compare of
+                // scatter_tracks_kernel wherever that cast is defined
+                if (x >= 0.f && x < (float)W && y >= 0.f && y < (float)H) k = (unsigned int)y * (unsigned int)W + (unsigned int)x;
+            }
+        }
+        keys[i] = k;
+    }
+    for (int i = threadIdx.x; i < max_id + 2; i += 1024) hist[i] = 0;
+    __syncthreads();
+    for (int k = 2; k <= cap; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = threadIdx.x; i < cap; i += 1024) {
+                const int ixj = i ^ j;
+                if (ixj > i) {
+                    const unsigned int a = keys[i], b = keys[ixj];
+                    if ((a > b) == ((i & k) == 0)) { keys[i] = b; keys[ixj] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    const float sh = (float)Hi / H, sw = (float)Wi / W;        // the nearest rule of point_id_hist_kernel
+    const int64_t *idf = ids + (long)t * Hi * Wi;
+    for (int i = threadIdx.x; i < cap; i += 1024) {
+        const unsigned int k = keys[i];
+        if (k == TRACK_KEY_NONE || (i > 0 && keys[i - 1] == k)) continue;
+        const int y = (int)(k / (unsigned int)W), x = (int)(k % (unsigned int)W);
+        int sy = (int)floorf(y * sh), sx = (int)floorf(x * sw);
+        sy = min(sy, Hi - 1); sx = min(sx, Wi - 1);
+        const int64_t id = idf[(long)sy * Wi + sx];
+        atomicAdd(&hist[max_id + 1], 1);
+        if (id >= 0 && id <= max_id) atomicAdd(&hist[(int)id], 1);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i <= max_id; i += 1024) counts[(long)t * (max_id + 1) + i] = hist[i];
+    if (threadIdx.x == 0) total[t] = hist[max_id + 1];
 }
 
 // presence[t][id] = id occurs in frame t of the id map (torch.unique of :680)
@@ -330,6 +392,29 @@ int s2d_point_id_counts(const uint8_t *point_masks, const int64_t *idmap, int T,
     if (s2d_zero_async(total, sizeof(int) * (size_t)T, stream) != S2D_OK) return S2D_ERR_LAUNCH;
     hipLaunchKernelGGL(point_id_hist_kernel, dim3(32, T), dim3(256), sizeof(int) * (max_id + 2), stream, point_masks, idmap, H, W,
                        Hi, Wi, max_id, counts, total);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_track_point_id_counts(const float *tracks, int T, int P, int H, int W, const int64_t *idmap, int Hi, int Wi, int max_id,
+                              int *counts, int *total, hipStream_t stream)
+{
+    if (max_id < 0 || max_id > 8190 || T < 0 || P < 0 || P > TRACK_MAX_POINTS) return S2D_ERR_ARG;
+    if (H < 1 || W < 1 || H >= (1 << 24) || W >= (1 << 24) || (long)H * W >= (long)TRACK_KEY_NONE) return S2D_ERR_ARG;
+    if (Hi < 1 || Wi < 1) return S2D_ERR_ARG;
+    if (T == 0) return S2D_OK;
+    int cap = 64;
+    while (cap < P) cap <<= 1;
+    const size_t lds = sizeof(unsigned int) * (size_t)cap + sizeof(int) * (size_t)(max_id + 2);   // <= 163,840 B
+    static S2dDevOnce set;
+    if (!set.done() && lds > 48 * 1024) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(track_point_id_counts_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                160 * 1024) != hipSuccess)
+            return S2D_ERR_LAUNCH;
+        set.mark();
+    }
+    hipLaunchKernelGGL(track_point_id_counts_kernel, dim3(T), dim3(1024), lds, stream, tracks, P, cap, H, W, idmap, Hi, Wi, max_id,
+                       counts, total);
     S2D_CHECK_LAUNCH();
     return S2D_OK;
 }

@@ -66,9 +66,9 @@ def select_masks(lbls, frames, objs):
     return out.cpu().numpy()
 
 
-def save_segmentation_masks(imgs, imgs_orig, lbls, meta, save_dir, debug=False):
+def save_segmentation_masks(imgs, imgs_orig, lbls, meta, save_dir, debug=False, return_masks=False):
     """keymask_utils.py:70-126, same signature and return value (the video's directory).  imgs / imgs_orig are only sliced
-    for debug prints in the reference and are not read here."""
+    for debug prints in the reference and are not read here.  return_masks: also return {(frame, mask): the uint8 mask written}."""
     per_cluster, video_name = extract_visibility_data(meta["visibility"])
     video_dir = os.path.join(save_dir, video_name)
     os.makedirs(video_dir, exist_ok=True)
@@ -82,6 +82,8 @@ def save_segmentation_masks(imgs, imgs_orig, lbls, meta, save_dir, debug=False):
         d = os.path.join(video_dir, f"cluster_{cid}")
         os.makedirs(d, exist_ok=True)
         Image.fromarray(m).save(os.path.join(d, f"cluster{cid}_frame{fid}_mask{mid}.png"))
+    if return_masks:
+        return video_dir, {(fid, mid): m for (_, fid, mid), m in zip(jobs, masks)}
     return video_dir
 
 

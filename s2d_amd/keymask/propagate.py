@@ -54,6 +54,24 @@ def point_id_counts(track_masks, idmap: IdMap):
     return counts, total
 
 
+TRACK_COUNTS_MAX_POINTS = 32768      # s2d_track_point_id_counts' LDS sort capacity (include/s2d_hip.h)
+
+
+def point_id_counts_from_tracks(pred_tracks, H, W, idmap: IdMap):
+    """pred_tracks [1,T,P,2] or [T,P,2] (x,y) in an H x W frame -> (counts int32 [T,max_id+1], total int32 [T]) on the device:
+    pred_tracks_to_binary_masks + point_id_counts in one launch, bit for bit on finite tracks (a point with a non-finite
+    coordinate is dropped).  More points than one workgroup's LDS sort holds take the two-launch path."""
+    tr = pred_tracks[0] if pred_tracks.dim() == 4 else pred_tracks
+    tr = tr.to(device="cuda", dtype=torch.float32).contiguous()
+    T, P, _ = tr.shape
+    if P > TRACK_COUNTS_MAX_POINTS:
+        return point_id_counts(pred_tracks_to_binary_masks(tr[None], H, W)[0], idmap)
+    counts = torch.empty((T, idmap.max_id + 1), device="cuda", dtype=torch.int32)
+    total = torch.empty((T,), device="cuda", dtype=torch.int32)
+    lib().call("s2d_track_point_id_counts", tr, T, P, H, W, idmap.ids, idmap.Hi, idmap.Wi, idmap.max_id, counts, total, _stream())
+    return counts, total
+
+
 def compute_point_mask_intersection(pointmask, mask, grid_size=None):
     """single pair, reference signature (:640-662): #(points & mask) / #points as a python float"""
     pm = (pointmask != 0).to(device="cuda", dtype=torch.uint8).contiguous()[None]
@@ -69,7 +87,17 @@ def extract_mask_matches(segm_mask_hw, pred_tracks, idmap: IdMap, v_range, match
     H, W = segm_mask_hw
     tm = pred_tracks_to_binary_masks(pred_tracks, H, W)[0]
     assert tm.shape[0] == idmap.T
-    counts, total = point_id_counts(tm, idmap)
+    return _matches_from_counts(*point_id_counts(tm, idmap), idmap, v_range, matching_threshold)
+
+
+def extract_mask_matches_from_tracks(segm_mask_hw, pred_tracks, idmap: IdMap, v_range, matching_threshold=0.5):
+    """extract_mask_matches through the fused kernel (point_id_counts_from_tracks): the same lists for finite tracks"""
+    H, W = segm_mask_hw
+    assert pred_tracks.shape[-3] == idmap.T
+    return _matches_from_counts(*point_id_counts_from_tracks(pred_tracks, H, W, idmap), idmap, v_range, matching_threshold)
+
+
+def _matches_from_counts(counts, total, idmap, v_range, matching_threshold):
     counts, total = counts.cpu().numpy(), total.cpu().numpy()      # ONE sync per tracked mask
     matches, allc = [], []
     for t in range(v_range[0], v_range[1] + 1):

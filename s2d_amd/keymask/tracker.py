@@ -1,0 +1,32 @@
+"""The point-tracker boundary of keymask discovery.
+
+A tracker is a callable with the call the reference makes (cotracker_occlusions.py:355, cotracker_matching.py:1071):
+
+    pred_tracks, pred_visibility = tracker(video, grid_size=g, grid_query_frame=f, segm_mask=m, backward_tracking=b)
+
+video float [1,T,3,H,W] (RGB, 0..255) on the device, segm_mask uint8 [1,1,H,W] with values {0,255} on the host;
+pred_tracks [1,T,N,2] (x, y) pixels and pred_visibility [1,T,N] bool.
+
+`load_tracker("cotracker", checkpoint)` builds CoTracker's offline predictor as the reference does (:318-328).  CoTracker is
+third party and optional: it is imported only there.  `load_tracker("pkg.module:attr")` imports a factory and calls it
+(with `checkpoint=` when one is given); that is how tests and other trackers plug in."""
+import importlib
+
+
+def load_tracker(spec, checkpoint=None):
+    if spec == "cotracker":
+        try:
+            from cotracker.predictor import CoTrackerPredictor
+        except ImportError as e:
+            raise ImportError("--tracker cotracker needs the `cotracker` package (CoTracker, facebookresearch/co-tracker), "
+                              "which is not installed; install it or pass --tracker pkg.module:factory") from e
+        if checkpoint is None:
+            raise ValueError("--tracker cotracker needs --tracker-checkpoint (e.g. scaled_offline.pth)")
+        model = CoTrackerPredictor(checkpoint=checkpoint)
+        import torch
+        return model.cuda() if torch.cuda.is_available() else model
+    mod, sep, attr = spec.partition(":")
+    if not sep or not mod or not attr:
+        raise ValueError(f"tracker spec {spec!r}: expected 'cotracker' or 'pkg.module:attr'")
+    factory = getattr(importlib.import_module(mod), attr)
+    return factory(checkpoint=checkpoint) if checkpoint is not None else factory()
