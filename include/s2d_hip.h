@@ -744,6 +744,22 @@ int s2d_copy_paste_u8(const uint8_t *tgt_frames, const uint8_t *tgt_masks, int N
                       const uint8_t *src_masks, int K, int Hs, int Ws, const int *paste_frames_dev, const uint8_t *keep_dev,
                       uint8_t *out_frames, uint8_t *out_masks, hipStream_t stream);
 
+/* ---- video demo rendering (s2d_amd/demo.py; model_training/demo_video/demo.py, predictor.py) ------------------------------------- */
+
+/* areas int32 [K][T] = set (non-zero) bytes of every plane of masks u8 [K][T][H][W] (the s2d_infer_masks_u8 layout; zeroed by the
+ * call); with order != null, order int32 [T][K] = per frame the instances in descending order of their area there, equal areas in
+ * instance order (a stable sort; numpy's argsort(-areas) for K <= 16).  K <= 255, T <= 65535; anything else returns S2D_ERR_ARG. */
+int s2d_mask_frame_areas_i32(const uint8_t *masks, int K, int T, int H, int W, int *areas, int *order, hipStream_t stream);
+
+/* The demo's overlay and mask index map in one pass.  frames u8 [T][H][W][3] (RGB) -> overlay u8 [T][H][W][3]: per frame the K
+ * instances are drawn in the order order int32 [T][K]; for instance k, every pixel p of its mask becomes
+ * (c_k * alpha + p * (256 - alpha) + 128) >> 8 per channel, and a mask pixel with a 4-neighbour outside the frame or outside mask k
+ * becomes c_k (colors u8 [K][3]).  index u8 [T][H][W] (skipped when null) = 1 + the highest k whose mask holds the pixel, 0 where
+ * none does.  K = 0 copies the frames.  Any alignment and row width; K <= 255, T <= 65535, 0 <= alpha <= 256; otherwise
+ * S2D_ERR_ARG. */
+int s2d_render_instances_u8(const uint8_t *frames, int T, int H, int W, const uint8_t *masks, int K, const int *order,
+                            const uint8_t *colors, int alpha, uint8_t *overlay, uint8_t *index, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -218,6 +218,7 @@ class KDVideoMaskFormer(nn.Module):
         self.teacher_aux_masks = False
         self.overlap_teacher, self._side = False, None
         self.inference_rle = False                  # eval branch: pred_masks as COCO RLE lists encoded on the device (inference_video rle=True)
+        self.inference_device_masks = False         # eval branch: pred_masks as the CUDA u8 [K,T,H,W] tensor (inference_video device_masks=True)
         self._side_delay_cycles = 0                 # tests only: spin the side stream this many cycles before the GT criterion
 
     @classmethod
@@ -563,17 +564,18 @@ class KDVideoMaskFormer(nn.Module):
         pred_labels, pred_masks}."""
         net = self.student if self.eval_student else self.teacher
         return _inference(net, images, batched_inputs, self.num_predictions_inference, self.use_nms, self.nms_threshold,
-                          rle=getattr(self, "inference_rle", False))
+                          rle=getattr(self, "inference_rle", False), device_masks=getattr(self, "inference_device_masks", False))
 
 
-def _inference(net, images, batched_inputs, num_predictions, use_nms, nms_threshold, rle=False):
+def _inference(net, images, batched_inputs, num_predictions, use_nms, nms_threshold, rle=False, device_masks=False):
     out = net(images, False)
     video = batched_inputs[0]
     first = video["image"][0]
     image_size = tuple(int(v) for v in first.shape[-2:])            # size without padding (images.image_sizes[0], :349)
     height, width = video.get("height", image_size[0]), video.get("width", image_size[1])   # :351-352
     return inference_video(out.class_logits[-1][0], out.mask_logits[-1][0], (out.T, out.hm, out.wm), tuple(images.shape[1:3]),
-                           image_size, (int(height), int(width)), num_predictions, use_nms, nms_threshold, rle=rle)
+                           image_size, (int(height), int(width)), num_predictions, use_nms, nms_threshold, rle=rle,
+                           device_masks=device_masks)
 
 
 @META_ARCH_REGISTRY.register()
@@ -589,6 +591,7 @@ class VideoMaskFormer(nn.Module):
         self.register_buffer("pixel_mean", torch.tensor(pixel_mean, dtype=torch.float32).view(-1, 1, 1), False)
         self.register_buffer("pixel_std", torch.tensor(pixel_std, dtype=torch.float32).view(-1, 1, 1), False)
         self.inference_rle = False                  # see KDVideoMaskFormer
+        self.inference_device_masks = False
 
     @classmethod
     def from_config(cls, cfg):  # video_maskformer_model.py:97-187 (the sparse-class / entropy / DropLoss variants are not on the path)
@@ -664,7 +667,8 @@ class VideoMaskFormer(nn.Module):
             net = lambda x, training: self.sem_seg_head(self.backbone(x), training)   # noqa: E731
             with torch.no_grad():
                 return _inference(net, images, batched_inputs, self.num_predictions, self.use_nms, self.nms_threshold,
-                                  rle=getattr(self, "inference_rle", False))
+                                  rle=getattr(self, "inference_rle", False),
+                                  device_masks=getattr(self, "inference_device_masks", False))
         Hp, Wp = images.shape[1:3]
         gt = TargetSet.from_list(_gt_target_list(batched_inputs, self.num_frames, Hp, Wp, self.device), device=self.device)
         params = [p for p in list(self.backbone.parameters()) + list(self.sem_seg_head.parameters()) if p.requires_grad]

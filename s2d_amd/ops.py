@@ -803,3 +803,39 @@ def mask_pair_counts(bits):
     inter = torch.empty((K, K), device=bits.device, dtype=torch.int64)
     lib().call("s2d_mask_pair_counts_u64", bits, K, words, inter, _stream())
     return inter
+
+
+def mask_frame_areas(masks, want_order=True):
+    """u8 masks [K,T,H,W] (the infer_masks layout) -> (areas int32 [K,T], draw order int32 [T,K] or None): per frame the instances
+    by descending area, ties in instance order.  K <= 255."""
+    _chk(masks, torch.uint8)
+    if masks.dim() != 4:
+        raise ValueError(f"masks must be [K, T, H, W], got {tuple(masks.shape)}")
+    K, T, H, W = masks.shape
+    if K > 255:
+        raise ValueError(f"at most 255 instances, got {K}")
+    areas = torch.empty((K, T), device=masks.device, dtype=torch.int32)
+    order = torch.empty((T, K), device=masks.device, dtype=torch.int32) if want_order else None
+    if K and T:
+        lib().call("s2d_mask_frame_areas_i32", masks, K, T, H, W, areas, order, _stream())
+    return areas, order
+
+
+def render_instances(frames, masks, order, colors, alpha=128, want_index=True):
+    """frames u8 RGB [T,H,W,3] (any byte offset), masks u8 [K,T,H,W], order int32 [T,K] (mask_frame_areas), colors u8 [K,3] ->
+    (overlay u8 [T,H,W,3], index map u8 [T,H,W] or None): the demo's raster rule (s2d_render_instances_u8)."""
+    _chk(frames, torch.uint8); _chk(masks, torch.uint8); _chk(order, torch.int32); _chk(colors, torch.uint8)
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError(f"frames must be [T, H, W, 3], got {tuple(frames.shape)}")
+    T, H, W, _ = frames.shape
+    K = masks.shape[0]
+    if K > 255:
+        raise ValueError(f"at most 255 instances, got {K}")
+    if tuple(masks.shape) != (K, T, H, W) or tuple(order.shape) != (T, K) or tuple(colors.shape) != (K, 3):
+        raise ValueError(f"shapes do not agree: frames {tuple(frames.shape)}, masks {tuple(masks.shape)}, order {tuple(order.shape)}, "
+                         f"colors {tuple(colors.shape)}")
+    overlay = torch.empty_like(frames, memory_format=torch.contiguous_format)
+    index = torch.empty((T, H, W), device=frames.device, dtype=torch.uint8) if want_index else None
+    if T and H and W:
+        lib().call("s2d_render_instances_u8", frames, T, H, W, masks, K, order, colors, int(alpha), overlay, index, _stream())
+    return overlay, index
