@@ -4,10 +4,15 @@
 Q=100, P=160000, 2 clips per GPU (BASELINE.json configs[3] shapes; forward+loss as BASELINE.json:metric says), encoder
 dropout 0.3 as every shipped config sets it (MODEL.MASK_FORMER.DROPOUT).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 --dump-outputs DIR writes what the timed path computed in its last timed step to DIR/<name>.npy (capture_outputs); the inputs,
 weights and seeds are fixed, so two builds run with the same arguments can be compared array for array.
+
+A plain run does only what the metric needs: set up, warm up, time the K steps, write the outputs, print the line.  --full also
+runs the reports that take runs of their own (each can be left out with its --no-* option): the other stream schedule with a
+bitwise comparison of the two schedules' losses, `amp`, `train_step`, `keymask` and `cpu_baseline` (the oracle on one 720p clip,
+minutes of host work).
 
 N > 1: one rank per GPU over RCCL.  Launched by `python -m torch.distributed.run ... bench.py --gpus N ...` the ranks read
 RANK / LOCAL_RANK / WORLD_SIZE; launched plainly with --gpus N > 1 this script starts those N ranks itself (child
@@ -15,9 +20,9 @@ processes, before this process touches a GPU) and exits with their status.
 
 One "step" = one pass of the hot path over one batch (2 clips x 8 frames per GPU) of synthetic input that is already
 resident in HBM.  Clips are independent units: ranks shard clips, forward+loss needs no collective (scaling: weak).
-Rank 0 prints ONE JSON line: the metric, `roofline` (dense kernels, live HIP events), `hbm_roofline` (whole step),
-`train_step` (one full training iteration incl. the RCCL gradient all-reduce at N > 1), `keymask` (BASELINE configs[2]
-kernel set, N = 1), `cpu_baseline` (N = 1).
+Rank 0 prints ONE JSON line: the metric, `hbm_roofline` (whole step), `roofline` (dense kernels, live HIP events: from the
+timed steps with --one-stream, from the other schedule's steps with --full) and, with --full, `train_step` (one full training
+iteration incl. the RCCL gradient all-reduce at N > 1), `keymask` (BASELINE configs[2] kernel set, N = 1), `cpu_baseline` (N = 1).
 """
 import argparse
 import json
@@ -491,7 +496,7 @@ def main():
     ap.add_argument("--no-kernel-events", action="store_true")
     ap.add_argument("--one-stream", "--no-overlap", dest="one_stream", action="store_true",
                     help="time the one-stream schedule (default: teacher forward + GT criterion on a second HIP stream; the other "
-                         "schedule is timed after the metric and reported under `schedules`, with a bitwise comparison of the losses)")
+                         "schedule is timed after the metric with --full and reported under `schedules`, with a bitwise comparison of the losses)")
     ap.add_argument("--clip-pipeline", dest="clip_pipeline", action="store_true", default=os.environ.get("S2D_CLIP_PIPELINE", "0") == "1",
                     help="process the batch clip by clip, clip b's criteria on a third stream beside clip b + 1's forwards "
                          "(KDVideoMaskFormer.pipeline_clips)")
@@ -508,9 +513,14 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the timed path computed in its last step (rank 0) to DIR/<name>.npy: "
                          "the weighted losses, their total, the student's final class logits and mask logits (a fixed sample if large)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the metric, also run the reports that take runs of their own: the other schedule and the bitwise "
+                         "comparison of both, amp, train_step, keymask, cpu_baseline (the --no-* options leave single ones out)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_other_schedule = args.no_amp = args.no_train_step = args.no_keymask = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))

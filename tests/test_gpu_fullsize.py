@@ -105,8 +105,8 @@ def test_two_stream_schedule_on_round1_attention_mask_source():
 
 
 def test_bench_two_ranks_share_the_gpu_gloo():
-    """bench.py --gpus 2 started without a launcher: it spawns its two ranks, they rendezvous (gloo: RCCL refuses two ranks on
-    one device), both run the metric step and the full training iteration incl. the gradient-arena all-reduce, and rank 0
+    """bench.py --gpus 2 --full started without a launcher: it spawns its two ranks, they rendezvous (gloo: RCCL refuses two ranks
+    on one device), both run the metric step and the full training iteration incl. the gradient-arena all-reduce, and rank 0
     prints one line with n_gpus == 2"""
     import json
     import os
@@ -117,7 +117,7 @@ def test_bench_two_ranks_share_the_gpu_gloo():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", "tiny", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -158,6 +158,40 @@ def test_bench_dump_outputs_reproducible(tmp_path):
         assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), n
     losses = [a for n, (a, _) in arrays.items() if "loss_" in n and n != "loss_total"]
     np.testing.assert_allclose(arrays["loss_total"][0], np.sum(losses, dtype=np.float64), rtol=1e-5)
+
+
+def test_bench_plain_run_is_lean_and_full_run_adds_the_reports(tmp_path):
+    """a plain bench.py run prints the metric line without the reports that take runs of their own; --full adds every one of
+    them after the timed steps and leaves the timed path alone: both runs dump the same arrays, bit for bit"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = {}
+    for name, extra in (("plain", []), ("full", ["--full"])):
+        d = str(tmp_path / name)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "tiny", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", d] + extra, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        runs[name] = (d, json.loads(lines[0]))
+    (dp, jp), (df, jf) = runs["plain"], runs["full"]
+    for j in (jp, jf):
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["value"] > 0 and j["ms_per_step"] > 0
+        assert j["unit"] == "clip-frames/s" and j["higher_is_better"] is True and j["dtype"] == jp["dtype"]
+    extras = ("amp", "train_step", "keymask", "cpu_baseline")
+    assert not any(k in jp for k in extras) and jp["schedules"]["other_ms_per_step"] is None, jp
+    assert jp["schedules"]["losses_bitwise_equal_between_schedules"] is None
+    assert all(k in jf and "error" not in jf[k] for k in extras), {k: jf.get(k) for k in extras}
+    assert jf["schedules"]["losses_bitwise_equal_between_schedules"] is True and jf["schedules"]["other_ms_per_step"] > 0
+    assert "roofline" in jf
+    names = sorted(os.listdir(dp))
+    assert names == sorted(os.listdir(df)) and jp["dumped_outputs"]["arrays"] == len(names)
+    for n in names:
+        a, b = np.load(os.path.join(dp, n)), np.load(os.path.join(df, n))
+        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), n
 
 
 def test_train_step_at_config4_gradients_finite_and_reproducible(setup):
