@@ -80,6 +80,39 @@ def _staging(n):
     return slot
 
 
+# The split-fp16 x3 arithmetic of the gradient kernels is fp32-class only for operand tensors whose amax lies in [2^-14, 65504] (DESIGN.md
+# "Dense arithmetic"); the raw gradients of the point losses are w (sigma - t) / (P * num_masks) * loss_scale at the root.  The
+# meta-archs' forward_backward multiplies the root gradients by a power of two S = grad_scale(loss_scale) and divides the parameter
+# gradients by it where they land (scale_grads): a power of two commutes exactly with every fp32 kernel of the backward, so only the bits
+# the split was losing change.  loss_scale * S is within a factor sqrt(2) of 2^GRAD_SCALE_LOG2, so the backward runs at the same
+# magnitudes whatever loss_scale (1 / ACCUM_ITER) is.  At the bench's c4 configuration the unscaled gradient operands span amax
+# 2.6e-5 .. 2.9 (scripts/split_operand_census.py, profiles/split_range/): 2^8 puts them at 6.8e-3 .. 7.3e2, inside [2^-14, 2^12].
+GRAD_SCALE_LOG2 = int(os.environ.get("S2D_GRAD_SCALE_LOG2", "8"))
+
+
+def grad_scale(loss_scale):
+    """the power of two S the root gradients are multiplied by on top of loss_scale (see GRAD_SCALE_LOG2)"""
+    import math
+    if not (loss_scale > 0 and math.isfinite(loss_scale)):
+        return 1.0
+    return math.ldexp(1.0, GRAD_SCALE_LOG2 - round(math.log2(loss_scale)))
+
+
+def scale_grads(params, factor):
+    """p.grad *= factor (a power of two: exact) for every parameter that has a non-empty gradient, in one multi-tensor pass; one gradient
+    tensor listed under several parameters is scaled once"""
+    if factor == 1.0:
+        return
+    seen, grads = set(), []
+    for p in params:
+        g = p.grad
+        if g is not None and g.numel() and (g.data_ptr(), g.numel()) not in seen:
+            seen.add((g.data_ptr(), g.numel()))
+            grads.append(g)
+    if grads:
+        torch._foreach_mul_(grads, float(factor))
+
+
 def acc(param, g):
     """accumulate a gradient into param.grad (allocating it on first use), as autograd's AccumulateGrad does"""
     g = g.reshape(param.shape)

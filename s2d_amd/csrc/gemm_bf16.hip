@@ -447,10 +447,12 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_w128_kernel(GemmParams p)
 
 // ------------------------------------------------------------------------------------------------------------
 // Split-fp16 x3 with a scaled low part ("f16x3"): fp32-class accuracy (~3*2^-22) at the same MFMA count.
-//   x = h + l * 2^-11,   h = fp16_rtz(x),   l = fp16_rtz((x - h) * 2^11)          (22+ significant bits, l never
-//   A.B^T = [Ah.Bh^T] + 2^-11 * [Ah.Bl^T + Al.Bh^T]                                 underflows relative to h)
+//   x = h + l * 2^-11,   h = fp16_rtz(x),   l = fp16_rtz((x - h) * 2^11)          (22+ significant bits while h is a
+//   A.B^T = [Ah.Bh^T] + 2^-11 * [Ah.Bl^T + Al.Bh^T]                                 normal fp16 number, |x| >= 2^-14)
 // The two brackets are accumulated in separate f32 accumulators (main / cross) and combined in the epilogue.
-// Operands must satisfy |x| < 65504 (fp16 range); the S2D activations and weights are O(1e-3..1e3).
+// The accuracy window is an operand amax in [2^-14, 65504]: below it h is subnormal or zero and l loses bits too (the error grows
+// ~10x per decade of scale), above it the RTZ conversion saturates (x -> 65535.98, no inf).  The forward's activations and weights
+// are O(1e-3..1e3); the gradients are brought into the window by the backward's power-of-two root scale (backward.grad_scale).
 typedef __fp16 h16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 

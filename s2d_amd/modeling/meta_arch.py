@@ -497,10 +497,18 @@ class KDVideoMaskFormer(nn.Module):
         for k, v in kd.items():
             losses[k.replace("loss_", "kd_loss_")] = v
         # ---- backward
+        from .. import backward as Bk
         NL, B = student.class_logits.shape[:2]
         Q, T, hm, wm = student.dims
         d_cls = torch.zeros_like(student.class_logits)
         sources = []
+        # the backward runs at the power-of-two root scale S (backward.grad_scale: its operands inside the split-fp16 window); .grad is
+        # brought to the same scale before the walk, so that accumulation adds like to like, and every part is scaled back before it is
+        # reported -- or, if the walk raises, on the way out
+        parts = {"predictor": list(head.predictor.parameters()), "pixel_decoder": list(head.pixel_decoder.parameters()),
+                 "backbone": list(backbone.parameters())}
+        S = Bk.grad_scale(loss_scale)
+        loss_scale = loss_scale * S
         for ctx, pre, strm in ((ctx_gt, "", crit_side), (ctx_kd, "kd_", main)):
             w_mask, w_dice = wd.get(pre + "loss_mask", 0.0), wd.get(pre + "loss_dice", 0.0)
             for i in range(NL - 1):
@@ -519,20 +527,26 @@ class KDVideoMaskFormer(nn.Module):
             if w_ce != 0.0:
                 d_cls[NL - 1] += ops.class_loss_backward(student.class_logits[NL - 1], ctx["idx_q"][(NL - 1) * B:].contiguous(),
                                                          ctx["n_match"][(NL - 1) * B:].contiguous(), w_ce * loss_scale, self.criterion.eos_coef)
-        from .. import backward as Bk
+        scaled = list(parts)             # parts whose .grad is at scale S
+        Bk.scale_grads([p for ps in parts.values() for p in ps], S)
         Bk.begin_deferred_acc()          # the ~350 "param.grad += g" of the walk below: one multi-tensor launch per part
         try:
             d_mf, d_mem = head.predictor.backward(td[0], d_cls, sources)
             Bk.flush_acc()
+            Bk.scale_grads(parts[scaled.pop(0)], 1.0 / S)
             if grad_ready is not None:
                 grad_ready("predictor")
             grads = head.pixel_decoder.backward_features(tp[0], d_mf, d_mem)
             Bk.flush_acc()
+            Bk.scale_grads(parts[scaled.pop(0)], 1.0 / S)
             if grad_ready is not None:
                 grad_ready("pixel_decoder")
             backbone.backward(tb, grads)
         finally:
-            Bk.flush_acc(end=True)
+            try:
+                Bk.flush_acc(end=True)
+            finally:
+                Bk.scale_grads([p for n in scaled for p in parts[n]], 1.0 / S)
         if grad_ready is not None:
             grad_ready("backbone")
         self.last = dict(student=student, teacher=teacher, kd_count=cnt, kd_kept=kept)
@@ -646,6 +660,10 @@ class VideoMaskFormer(nn.Module):
         for i in range(NL - 1):
             if wd.get(f"loss_mask_{i}", w_mask) != w_mask or wd.get(f"loss_dice_{i}", w_dice) != w_dice:
                 raise NotImplementedError("per-layer loss weights that differ between decoder layers")
+        from .. import backward as Bk
+        params = list(self.backbone.parameters()) + list(head.parameters())
+        S = Bk.grad_scale(loss_scale)                 # the root scale of the backward (see KDVideoMaskFormer.forward_backward)
+        loss_scale = loss_scale * S
         sources = []
         if w_mask != 0.0 or w_dice != 0.0:
             rows = ops.point_loss_backward(ctx["point_loss"], w_mask * loss_scale, w_dice * loss_scale).view(NL, B, ctx["maxm"], T * hm * wm)
@@ -654,8 +672,12 @@ class VideoMaskFormer(nn.Module):
         if w_ce != 0.0:
             d_cls[NL - 1] = ops.class_loss_backward(out.class_logits[NL - 1], ctx["idx_q"][(NL - 1) * B:].contiguous(),
                                                     ctx["n_match"][(NL - 1) * B:].contiguous(), w_ce * loss_scale, self.criterion.eos_coef)
-        d_mf, d_mem = head.predictor.backward(td[0], d_cls, sources)
-        self.backbone.backward(tb, head.pixel_decoder.backward_features(tp[0], d_mf, d_mem))
+        Bk.scale_grads(params, S)
+        try:
+            d_mf, d_mem = head.predictor.backward(td[0], d_cls, sources)
+            self.backbone.backward(tb, head.pixel_decoder.backward_features(tp[0], d_mf, d_mem))
+        finally:
+            Bk.scale_grads(params, 1.0 / S)
         self.last = dict(outputs=out)
         return {k: v * wd[k] for k, v in losses.items() if k in wd}
 

@@ -143,8 +143,9 @@ def _static_split(B, N, K, ldb):
 
 
 def set_dense_mode(mode):
-    """"f16x3" (default: split-fp16 x3 on the f16 MFMA, ~3e-7 relative), "bf16x3" (split-bf16 x3, ~5e-6, no range
-    limit) or "f32" (fp32-input MFMA, exact f32 FMA chain)."""
+    """"f16x3" (default: split-fp16 x3 on the f16 MFMA, ~3e-7 relative while every operand tensor's amax lies in [2^-14, 65504];
+    below that the error grows ~10x per decade of operand scale, above it the split saturates at 65535.98), "bf16x3" (split-bf16 x3,
+    ~5e-6, no range limit) or "f32" (fp32-input MFMA, exact f32 FMA chain)."""
     global _MODE
     lib().call("s2d_set_dense_mode", {"f32": 0, "bf16x3": 1, "f16x3": 2}[mode])
     _MODE = mode
