@@ -334,6 +334,15 @@ int s2d_matcher_cost_f32(const float *mask_logits, const float *class_logits, co
                          int W, int Nmax, int P, float w_class, float w_mask, float w_dice, float *workspace, float *C,
                          hipStream_t stream);
 
+/* Class-aware heads: s2d_matcher_cost_f32 on class_logits [NL][B][Q][C1] (C1 = C + 1 >= 2), class term -softmax_C1(l)[0]
+ * (matcher.py:235-243: tgt_ids zeroed).  The workspace is s2d_matcher_c_workspace_floats floats (the cost pipeline's + the
+ * [NL*B][Q] class column).  At C1 = 2 the cost matrix equals s2d_matcher_cost_f32's bit for bit. */
+long s2d_matcher_c_workspace_floats(int NL, int B, int Q, int T, int P, int H, int W);
+int s2d_matcher_cost_c_f32(const float *mask_logits, const float *class_logits, int C1, const uint8_t *tgt, const int *tgt_count,
+                           const float *coords, uint64_t seed, int NL, int B, int Q, int ldq, int T, int hm, int wm, int H,
+                           int W, int Nmax, int P, float w_class, float w_mask, float w_dice, float *workspace, float *C,
+                           hipStream_t stream);
+
 /* scipy.optimize.linear_sum_assignment (matcher.py:289) for nprob cost matrices C[problem][Q][Nmax] using the
  * first tgt_count[problem % B] columns.  idx_q/idx_t [nprob][min(Q,Nmax)] receive (query, target) pairs in scipy's
  * order (queries ascending), n_match[nprob] their number = min(Q, N).  Q <= 128, Nmax <= 128, Q*Nmax <= 12800. */
@@ -349,6 +358,16 @@ int s2d_lsap_f32(const float *C, const int *tgt_count, int nprob, int B, int Q, 
 int s2d_kd_targets_u8(const float *t_class_logits, const float *t_mask_logits, float score_thr, int topk, int B, int Q,
                       int ldq, int T, int hm, int wm, int H, int W, int Nmax, uint8_t *tgt, int *count, int *kept_q,
                       int *nonempty, hipStream_t stream);
+
+/* Class-aware s2d_kd_targets_u8 (kd_video_maskformer_model.py:436-468 with C = C1 - 1 >= 1 classes): top-`topk` over the
+ * flattened softmax(l)[:, :-1] scores [Q*C] of each clip, kept when >= score_thr, emitted in ascending flat index q*C + c
+ * (the order of the reference's topk(sorted=False) is undefined; at C = 1 this is s2d_kd_targets_u8's ascending query order).
+ * label[b][n] = the pseudo target's class; a query may give several targets (one per label), each with its own plane.
+ * workspace: s2d_kd_targets_c_workspace_bytes(B, Q, C1) bytes. */
+long s2d_kd_targets_c_workspace_bytes(int B, int Q, int C1);
+int s2d_kd_targets_c_u8(const float *t_class_logits, int C1, const float *t_mask_logits, float score_thr, int topk, int B, int Q,
+                        int ldq, int T, int hm, int wm, int H, int W, int Nmax, void *workspace, uint8_t *tgt, int *count, int *kept_q,
+                        int *label, int *nonempty, hipStream_t stream);
 
 /* nonempty[b][n][t] = any(tgt[b][n][t]) for ground-truth targets (criterion.py:310-313). H*W % 16 == 0. */
 int s2d_target_nonempty(const uint8_t *tgt, const int *count, int B, int Nmax, int T, int H, int W, int *nonempty,
@@ -375,6 +394,11 @@ int s2d_point_loss_f32(const float *mask_logits, const uint8_t *tgt, const int *
 int s2d_class_loss_f32(const float *class_logits, const int *idx_q, const int *n_match, int B, int Q, int maxm,
                        float eos_coef, float *loss_ce, hipStream_t stream);
 
+/* s2d_class_loss_f32 on class_logits [B][Q][C1] (C1 >= 2): matched queries target class 0, the others class C1 - 1, weighted CE
+ * with empty_weight (1, ..., 1, eos_coef) (criterion.py:227-251).  C1 = 2 gives s2d_class_loss_f32's bits. */
+int s2d_class_loss_c_f32(const float *class_logits, int C1, const int *idx_q, const int *n_match, int B, int Q, int maxm,
+                         float eos_coef, float *loss_ce, hipStream_t stream);
+
 /* ---- eval-side step after the path: inference_video -------------------------------- */
 
 /* kd_video_maskformer_model.py:532-538 (= video_maskformer_model.py:300-306): scores = softmax(class_logits
@@ -382,6 +406,12 @@ int s2d_class_loss_f32(const float *class_logits, const int *idx_q, const int *n
  * flat // C, label[K] = flat % C on the device.  Q*C <= 16384, 1 <= K <= Q*C. */
 int s2d_infer_select_f32(const float *class_logits, int Q, int C, int K, float *scores, int *query, int *label,
                          hipStream_t stream);
+
+/* s2d_infer_select_f32 for any Q * C (no LDS bound; C = C1 - 1), same scores, sorted order and tie rule (equal scores: lower flat
+ * index q*C + c first).  workspace: s2d_infer_select_c_workspace_bytes(Q, C1) bytes. */
+long s2d_infer_select_c_workspace_bytes(int Q, int C1);
+int s2d_infer_select_c_f32(const float *class_logits, int Q, int C1, int K, void *workspace, float *scores, int *query, int *label,
+                           hipStream_t stream);
 
 /* floats of workspace s2d_infer_masks_u8 needs (the K gathered low-resolution planes) */
 long s2d_infer_workspace_floats(int K, int T, int hm, int wm);
@@ -619,6 +649,10 @@ int s2d_point_loss_rng_points(uint64_t seed, int hm, int wm, int row0, int nrows
 /* d(w_ce * loss_labels)/d(class_logits) for one layer (same arguments as s2d_class_loss_f32) -> [B][Q][2] */
 int s2d_class_loss_backward_f32(const float *class_logits, const int *idx_q, const int *n_match, int B, int Q, int maxm,
                                 float eos_coef, float w_ce, float *d_class_logits, hipStream_t stream);
+
+/* d(w_ce * loss_labels)/d(class_logits) for class_logits [B][Q][C1] (same arguments as s2d_class_loss_c_f32) -> [B][Q][C1] */
+int s2d_class_loss_backward_c_f32(const float *class_logits, int C1, const int *idx_q, const int *n_match, int B, int Q, int maxm,
+                                  float eos_coef, float w_ce, float *d_class_logits, hipStream_t stream);
 
 /* ---- keymask discovery (paths relative to /root/reference/keymask_ident) ------------------------------- */
 

@@ -7,7 +7,14 @@
 
 Tensors whose shape differs from the model's are skipped with a warning, as detectron2's checkpointer does.  The library's
 modules cache packed / pre-split images of their weights; those are dropped here, so weights loaded into a model that has
-already run a forward take effect.  `.pkl` model-zoo files are not read."""
+already run a forward take effect.
+
+detectron2 `.pkl` files ({"model": {name: ndarray}, "__author__": ..., ["matching_heuristics": True]}, pickled with
+encoding="latin1") are read through a restricted unpickler that admits numpy arrays, numpy scalars and plain containers only.
+Exact detectron2 model names go through the same conversions as a .pth; the backbone-only ImageNet files
+(torchvision-converted names stem.* / res2.* ... res5.*) are mapped onto backbone.* (student.0.* and teacher.0.* in a KD
+model).  detectron2's general suffix-matching heuristic (`matching_heuristics`) is not implemented: names that match neither
+form are reported as unexpected, like any other unmatched key."""
 import logging
 import pickle
 
@@ -53,10 +60,49 @@ def convert_state_dict(sd, model_keys):
     return dict(sd)
 
 
+_BACKBONE_TOP = ("stem.", "res2.", "res3.", "res4.", "res5.")
+
+# what a detectron2 .pkl may contain: ndarray reconstruction and dtypes, numpy scalars, plain containers
+_PKL_ALLOWED = {
+    ("numpy.core.multiarray", "_reconstruct"), ("numpy._core.multiarray", "_reconstruct"),
+    ("numpy.core.multiarray", "scalar"), ("numpy._core.multiarray", "scalar"),
+    ("numpy", "ndarray"), ("numpy", "dtype"),
+    ("collections", "OrderedDict"), ("builtins", "dict"), ("builtins", "list"), ("builtins", "tuple"), ("builtins", "set"),
+}
+
+
+class _ArrayUnpickler(pickle.Unpickler):
+    """refuses every global outside _PKL_ALLOWED (a .pkl could otherwise run arbitrary code when loaded)"""
+
+    def find_class(self, module, name):
+        if (module, name) in _PKL_ALLOWED:
+            return super().find_class(module, name)
+        raise pickle.UnpicklingError(f"refusing {module}.{name} in a .pkl checkpoint: only numpy arrays, numpy scalars and plain "
+                                     "containers are read")
+
+
+def read_pkl(path):
+    """a detectron2 .pkl -> {name: tensor}.  Backbone-only files (every name under stem. / res2. ... res5.) get the backbone.
+    prefix so that the plain / KD conversions place them."""
+    with open(path, "rb") as f:
+        data = _ArrayUnpickler(f, encoding="latin1").load()
+    sd = data["model"] if isinstance(data, dict) and "model" in data else data
+    if not isinstance(sd, dict):
+        raise pickle.UnpicklingError(f"{path}: expected a dict of arrays, found {type(sd).__name__}")
+    out = {}
+    for k, v in sd.items():
+        if not isinstance(v, (np.ndarray, np.generic)):
+            raise pickle.UnpicklingError(f"{path}: entry {k!r} is a {type(v).__name__}, not a numpy array")
+        out[k] = torch.from_numpy(np.array(v))
+    if out and all(k.startswith(_BACKBONE_TOP) for k in out):
+        out = {"backbone." + k: v for k, v in out.items()}
+    return out
+
+
 def read_state_dict(path):
-    """a torch .pth -> its state dict (the "model" entry when there is one)"""
+    """a torch .pth or a detectron2 .pkl -> its state dict (the "model" entry when there is one)"""
     if path.endswith(".pkl"):
-        raise NotImplementedError(".pkl model-zoo checkpoints are not supported: convert them to a torch .pth")
+        return read_pkl(path)
     try:
         ckpt = torch.load(path, map_location="cpu", weights_only=True)
     except pickle.UnpicklingError:
@@ -78,7 +124,7 @@ def invalidate_weight_caches(model):
 
 
 def load_checkpoint(model, path_or_state_dict):
-    """load a .pth (or a state dict) into `model` -> {"missing": [...], "unexpected": [...], "mismatched": [(key, ckpt shape,
+    """load a .pth / .pkl (or a state dict) into `model` -> {"missing": [...], "unexpected": [...], "mismatched": [(key, ckpt shape,
     model shape)]}"""
     sd = path_or_state_dict if isinstance(path_or_state_dict, dict) else read_state_dict(path_or_state_dict)
     own = model.state_dict()

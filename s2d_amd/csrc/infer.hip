@@ -15,6 +15,7 @@
 // bit words; a tiled popcount kernel turns the bit words into the K x K intersection counts, from which the host runs
 // the greedy loop without touching the masks again.
 #include "common.h"
+#include "class_select.h"
 
 namespace {
 
@@ -263,6 +264,19 @@ int s2d_infer_select_f32(const float *cls_logits, int Q, int C, int K, float *sc
     const size_t lds = sizeof(float) * (size_t)Q * C;
     if (lds > 64 * 1024) return S2D_ERR_ARG;
     hipLaunchKernelGGL(infer_select_kernel, dim3(1), dim3(SEL_THREADS), lds, stream, cls_logits, Q, C, K, scores, query, label);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+long s2d_infer_select_c_workspace_bytes(int Q, int C1) { return C1 < 2 ? 0 : cls_select_workspace_bytes(1, Q, C1); }
+
+// s2d_infer_select_f32 for any Q*C (class_select.h): the same scores, order and tie rule, without the 64 KB LDS bound
+int s2d_infer_select_c_f32(const float *cls_logits, int Q, int C1, int K, void *workspace, float *scores, int *query, int *label,
+                           hipStream_t stream)
+{
+    if (Q < 1 || C1 < 2 || K < 1 || (long)K > (long)Q * (C1 - 1) || (long)Q * (C1 - 1) > 0x7FFFFFFFL / 2) return S2D_ERR_ARG;
+    int *rank = nullptr;
+    cls_select_launch(cls_logits, 1, Q, C1, K, -1.f, workspace, &rank, scores, query, label, stream);
     S2D_CHECK_LAUNCH();
     return S2D_OK;
 }

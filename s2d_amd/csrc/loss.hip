@@ -13,6 +13,7 @@
 // counter-based RNG keyed by (seed, row, index), so re-sampling in every pass is free of HBM traffic.
 // All partial sums land in fixed slots and are reduced in a fixed order (double): deterministic losses.
 #include "common.h"
+#include "class_select.h"
 
 namespace {
 
@@ -1387,7 +1388,120 @@ __global__ void class_loss_backward_kernel(const float *__restrict__ cls, const 
     }
 }
 
+// class_loss_kernel over C1 logits per query: matched -> class 0, others -> class C1 - 1 (= no object; criterion.py:227-251 with the
+// target labels zeroed).  Same per-query expression tree (max, then sum of exp in class order) and the same fixed-order reduction,
+// so C1 = 2 gives class_loss_kernel's bits.
+__global__ void class_loss_c_kernel(const float *__restrict__ cls, int C1, const int *__restrict__ idx_q, const int *__restrict__ n_match,
+                                    int B, int Q, int maxm, float eos, float *__restrict__ out)
+{
+    __shared__ unsigned char matched[128];
+    __shared__ double wnum[16], wden[16];
+    double num = 0., den = 0.;
+    for (int b = 0; b < B; ++b) {
+        __syncthreads();
+        if (threadIdx.x < 128) matched[threadIdx.x] = 0;
+        __syncthreads();
+        if (threadIdx.x < n_match[b]) matched[idx_q[(long)b * maxm + threadIdx.x]] = 1;
+        __syncthreads();
+        const int q = threadIdx.x;
+        if (q < Q) {
+            const float *l = cls + ((long)b * Q + q) * C1;
+            float mx, sum;
+            softmax_row_stats(l, C1, mx, sum);
+            const float lse = mx + logf(sum);
+            const bool m = matched[q];
+            const float w = m ? 1.f : eos;
+            num += (double)(w * (lse - (m ? l[0] : l[C1 - 1])));
+            den += (double)w;
+        }
+    }
+    num = wave_sum_d(num); den = wave_sum_d(den);
+    if ((threadIdx.x & 63) == 0) { wnum[threadIdx.x >> 6] = num; wden[threadIdx.x >> 6] = den; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double sn = 0., sd = 0.;
+        for (unsigned int w = 0; w < (blockDim.x + 63) / 64; ++w) { sn += wnum[w]; sd += wden[w]; }   // fixed order
+        out[0] = (float)(sn / sd);
+    }
+}
+
+// class_loss_backward_kernel over C1 logits: one workgroup per clip, a query's C1 gradients written by consecutive lanes
+__global__ __launch_bounds__(256) void class_loss_backward_c_kernel(const float *__restrict__ cls, int C1, const int *__restrict__ idx_q,
+                                                                    const int *__restrict__ n_match, int B, int Q, int maxm, float eos,
+                                                                    float w_ce, float *__restrict__ dcls)
+{
+    __shared__ unsigned char matched[128];
+    __shared__ float mxs[128], sums[128];
+    const int b = blockIdx.x;
+    double den = 0.;
+    for (int bb = 0; bb < B; ++bb) den += (double)n_match[bb] + (double)eos * (Q - n_match[bb]);
+    const float wsum = (float)den;
+    if (threadIdx.x < 128) matched[threadIdx.x] = 0;
+    __syncthreads();
+    if ((int)threadIdx.x < n_match[b]) matched[idx_q[(long)b * maxm + threadIdx.x]] = 1;
+    if ((int)threadIdx.x < Q) {
+        float mx, sum;
+        softmax_row_stats(cls + ((long)b * Q + threadIdx.x) * C1, C1, mx, sum);
+        mxs[threadIdx.x] = mx; sums[threadIdx.x] = sum;
+    }
+    __syncthreads();
+    const long n = (long)Q * C1;
+    for (long i = threadIdx.x; i < n; i += 256) {
+        const int q = (int)(i / C1), c = (int)(i - (long)q * C1);
+        const float e = expf(cls[(long)b * n + i] - mxs[q]);
+        const float pc = e / sums[q];
+        const bool m = matched[q];
+        const float w = (m ? 1.f : eos) * w_ce / wsum;
+        const float onehot = (c == (m ? 0 : C1 - 1)) ? 1.f : 0.f;
+        dcls[(long)b * n + i] = w * (pc - onehot);
+    }
+}
+
+// kd_select_kernel's outputs from the flat ranks of class_select.h: targets are the top-K flat scores that reach the threshold
+// (rank < K; a non-candidate has rank n >= K), emitted in ascending flat index q*C + c, so a query may appear once per label.
+// One workgroup per clip walks the ranks in 256-wide steps with a ballot prefix count.
+__global__ __launch_bounds__(256) void kd_compact_kernel(const int *__restrict__ rank, int n, int C, int K, int Nmax, int *__restrict__ count,
+                                                         int *__restrict__ kept, int *__restrict__ label)
+{
+    __shared__ int wcnt[4];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int base = 0;
+    for (int j0 = 0; j0 < n; j0 += 256) {
+        const int i = j0 + threadIdx.x;
+        const bool keep = i < n && rank[(long)b * n + i] < K;
+        const unsigned long long bal = __ballot(keep);
+        const int before = __popcll(bal & ((1ull << lane) - 1ull));
+        __syncthreads();
+        if (lane == 0) wcnt[w] = __popcll(bal);
+        __syncthreads();
+        int off = base + before;
+        for (int v = 0; v < w; ++v) off += wcnt[v];
+        if (keep && off < Nmax) {
+            kept[(long)b * Nmax + off] = i / C;
+            label[(long)b * Nmax + off] = i % C;
+        }
+        base += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    }
+    if (threadIdx.x == 0) count[b] = base < Nmax ? base : Nmax;
+}
+
 }  // namespace
+
+// masks of the selected queries, upsampled and thresholded into tgt / nonempty (the launches shared by both selections)
+static int kd_upsample_launch(const float *t_mask_logits, int B, int ldq, int T, int hm, int wm, int H, int W, int Nmax, uint8_t *tgt,
+                              const int *count, const int *kept_q, int *nonempty, hipStream_t stream)
+{
+    // tiled form: whole 4-column groups, 32-bit stores, and a tile's source window inside the staged 8 x 72 pixels
+    // (floor(s (o + 15.5) - 0.5) + 1 - floor(s (o + 0.5) - 0.5) <= 16 s + 2 rows, 256 s + 2 columns)
+    if (W % 4 == 0 && (reinterpret_cast<uintptr_t>(tgt) & 3) == 0 && 16L * hm + 2L * H <= (long)KDT_SH * H && 256L * wm + 2L * W <= (long)KDT_SW * W)
+        hipLaunchKernelGGL(kd_upsample_tile_kernel, dim3(cdiv(W, KDT_W), cdiv(H, KDT_H), B * T), dim3(256), 0, stream, t_mask_logits, ldq, T, hm, wm,
+                           H, W, Nmax, count, kept_q, tgt, nonempty);
+    else
+        hipLaunchKernelGGL(kd_upsample_kernel, dim3(cdiv(W, 256), H, B * T), dim3(256), 0, stream, t_mask_logits, ldq, T, hm, wm,
+                           H, W, Nmax, count, kept_q, tgt, nonempty);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
 
 extern "C" {
 
@@ -1400,17 +1514,28 @@ int s2d_kd_targets_u8(const float *t_class_logits, const float *t_mask_logits, f
     if (s2d_zero_async(nonempty, sizeof(int) * (size_t)B * Nmax * T, stream) != S2D_OK) return S2D_ERR_LAUNCH;
     hipLaunchKernelGGL(kd_select_kernel, dim3(B), dim3(128), 0, stream, t_class_logits, Q, topk < Q ? topk : Q, score_thr,
                        Nmax, count, kept_q);
-    // tiled form: whole 4-column groups, 32-bit stores, and a tile's source window inside the staged 8 x 72 pixels
-    // (floor(s (o + 15.5) - 0.5) + 1 - floor(s (o + 0.5) - 0.5) <= 16 s + 2 rows, 256 s + 2 columns)
-    if (W % 4 == 0 && (reinterpret_cast<uintptr_t>(tgt) & 3) == 0 && 16L * hm + 2L * H <= (long)KDT_SH * H && 256L * wm + 2L * W <= (long)KDT_SW * W)
-        hipLaunchKernelGGL(kd_upsample_tile_kernel, dim3(cdiv(W, KDT_W), cdiv(H, KDT_H), B * T), dim3(256), 0, stream, t_mask_logits, ldq, T, hm, wm,
-                           H, W, Nmax, count, kept_q, tgt, nonempty);
-    else
-        hipLaunchKernelGGL(kd_upsample_kernel, dim3(cdiv(W, 256), H, B * T), dim3(256), 0, stream, t_mask_logits, ldq, T, hm, wm,
-                           H, W, Nmax, count, kept_q, tgt, nonempty);
-    S2D_CHECK_LAUNCH();
-    return S2D_OK;
+    return kd_upsample_launch(t_mask_logits, B, ldq, T, hm, wm, H, W, Nmax, tgt, count, kept_q, nonempty, stream);
 }
+
+long s2d_kd_targets_c_workspace_bytes(int B, int Q, int C1)
+{
+    return C1 < 2 ? 0 : cls_select_workspace_bytes(B, Q, C1);
+}
+
+int s2d_kd_targets_c_u8(const float *t_class_logits, int C1, const float *t_mask_logits, float score_thr, int topk, int B, int Q,
+                        int ldq, int T, int hm, int wm, int H, int W, int Nmax, void *workspace, uint8_t *tgt, int *count, int *kept_q,
+                        int *label, int *nonempty, hipStream_t stream)
+{
+    if (Q > 128 || Nmax > 128 || C1 < 2 || topk < 0 || (long)Q * (C1 - 1) > 0x7FFFFFFFL / 2) return S2D_ERR_ARG;
+    if (B == 0) return S2D_OK;
+    const int n = Q * (C1 - 1);
+    if (s2d_zero_async(nonempty, sizeof(int) * (size_t)B * Nmax * T, stream) != S2D_OK) return S2D_ERR_LAUNCH;
+    int *rank = nullptr;
+    cls_select_launch(t_class_logits, B, Q, C1, topk < n ? topk : n, score_thr, workspace, &rank, nullptr, nullptr, nullptr, stream);
+    hipLaunchKernelGGL(kd_compact_kernel, dim3(B), dim3(256), 0, stream, rank, n, C1 - 1, topk < n ? topk : n, Nmax, count, kept_q, label);
+    return kd_upsample_launch(t_mask_logits, B, ldq, T, hm, wm, H, W, Nmax, tgt, count, kept_q, nonempty, stream);
+}
+
 
 int s2d_target_nonempty(const uint8_t *tgt, const int *count, int B, int Nmax, int T, int H, int W, int *nonempty,
                         hipStream_t stream)
@@ -1625,6 +1750,27 @@ int s2d_class_loss_f32(const float *class_logits, const int *idx_q, const int *n
     if (Q > 128) return S2D_ERR_ARG;
     hipLaunchKernelGGL(class_loss_kernel, dim3(1), dim3(128), 0, stream, class_logits, idx_q, n_match, B, Q, maxm, eos_coef,
                        loss_ce);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_class_loss_c_f32(const float *class_logits, int C1, const int *idx_q, const int *n_match, int B, int Q, int maxm,
+                         float eos_coef, float *loss_ce, hipStream_t stream)
+{
+    if (Q > 128 || C1 < 2) return S2D_ERR_ARG;
+    hipLaunchKernelGGL(class_loss_c_kernel, dim3(1), dim3(128), 0, stream, class_logits, C1, idx_q, n_match, B, Q, maxm, eos_coef,
+                       loss_ce);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_class_loss_backward_c_f32(const float *class_logits, int C1, const int *idx_q, const int *n_match, int B, int Q, int maxm,
+                                  float eos_coef, float w_ce, float *d_class_logits, hipStream_t stream)
+{
+    if (Q > 128 || C1 < 2) return S2D_ERR_ARG;
+    if (B == 0) return S2D_OK;
+    hipLaunchKernelGGL(class_loss_backward_c_kernel, dim3(B), dim3(256), 0, stream, class_logits, C1, idx_q, n_match, B, Q, maxm,
+                       eos_coef, w_ce, d_class_logits);
     S2D_CHECK_LAUNCH();
     return S2D_OK;
 }

@@ -666,6 +666,9 @@ __global__ __launch_bounds__(256, 2) void matcher_cost_f16_mix_kernel(CostParams
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void matcher_cost_f16_q16_kernel(CostParams p) { matcher_cost_f16_body<1>(p); }
 
 // C[prob][q][n] = w_mask*cost_mask + w_class*(-softmax(logits)[q][0]) + w_dice*cost_dice   (matcher.py:280-287)
+// COL: the class term is read from a precomputed column prob0[prob][q] = softmax_C1(logits)[0] (class-aware heads, C1 > 2) instead
+// of being formed from two logits; at C1 = 2 the column holds e0 / (e0 + e1) bit for bit, the value formed here.
+template <bool COL = false>
 __global__ void matcher_finalize_kernel(CostParams p, const float *__restrict__ cls, float wc, float wm_, float wd,
                                         float *__restrict__ C)
 {
@@ -689,13 +692,31 @@ __global__ void matcher_finalize_kernel(CostParams p, const float *__restrict__ 
         const double TP = (double)p.T * p.P;
         const double cost_mask = (SP - A) / TP;
         const double cost_dice = 1.0 - (2.0 * D + 1.0) / (SG + ST + 1.0);
-        const float l0 = cls[((long)prob * p.Q + q) * 2], l1 = cls[((long)prob * p.Q + q) * 2 + 1];
-        const float mx = fmaxf(l0, l1);
-        const float e0 = expf(l0 - mx), e1 = expf(l1 - mx);
-        const double prob0 = (double)(e0 / (e0 + e1));
+        double prob0;
+        if (COL) {
+            prob0 = (double)cls[(long)prob * p.Q + q];
+        } else {
+            const float l0 = cls[((long)prob * p.Q + q) * 2], l1 = cls[((long)prob * p.Q + q) * 2 + 1];
+            const float mx = fmaxf(l0, l1);
+            const float e0 = expf(l0 - mx), e1 = expf(l1 - mx);
+            prob0 = (double)(e0 / (e0 + e1));
+        }
         out = (float)((double)wm_ * cost_mask + (double)wc * (-prob0) + (double)wd * cost_dice);
     }
     C[((long)prob * p.Q + q) * p.Nmax + n] = out;
+}
+
+// prob0[row] = softmax(cls[row][0 .. C1-1])[0], max and sum of exp formed in class order (the two-logit kernels' expression tree)
+__global__ __launch_bounds__(256) void class_prob0_kernel(const float *__restrict__ cls, long rows, int C1, float *__restrict__ prob0)
+{
+    const long r = (long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const float *l = cls + r * C1;
+    float mx = l[0];
+    for (int c = 1; c < C1; ++c) mx = fmaxf(mx, l[c]);
+    float sum = 0.f;
+    for (int c = 0; c < C1; ++c) sum += expf(l[c] - mx);
+    prob0[r] = expf(l[0] - mx) / sum;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -827,10 +848,13 @@ long s2d_matcher_workspace_floats(int NL, int B, int T, int P, int H, int W)
     return nprob * ch * (2L * QP * NP + 3 * 128) + 4 * n + 4 * n + (4 * n + (1L << 20)) + 64 + (long)B * T * H * W;
 }
 
-int s2d_matcher_cost_f32(const float *mask_logits, const float *class_logits, const uint8_t *tgt, const int *tgt_count,
-                         const float *coords, uint64_t seed, int NL, int B, int Q, int ldq, int T, int hm, int wm, int H,
-                         int W, int Nmax, int P, float w_class, float w_mask, float w_dice, float *workspace, float *C,
-                         hipStream_t stream)
+}  // extern "C"
+
+// the cost pipeline; prob0 != null: the class term comes from that [NL*B][Q] column (s2d_matcher_cost_c_f32)
+static int matcher_cost_impl(const float *mask_logits, const float *class_logits, const float *prob0, const uint8_t *tgt,
+                             const int *tgt_count, const float *coords, uint64_t seed, int NL, int B, int Q, int ldq, int T, int hm,
+                             int wm, int H, int W, int Nmax, int P, float w_class, float w_mask, float w_dice, float *workspace,
+                             float *C, hipStream_t stream)
 {
     if (Q > QP || Nmax > NP || Q <= 0 || Nmax <= 0 || ldq < Q) return S2D_ERR_ARG;
     const int nprob = NL * B;
@@ -890,10 +914,45 @@ int s2d_matcher_cost_f32(const float *mask_logits, const float *class_logits, co
     else if (mix) hipLaunchKernelGGL(matcher_cost_f16_mix_kernel, dim3(grid), dim3(256), lds_rows, stream, p);
     else hipLaunchKernelGGL(matcher_cost_f16_kernel, dim3(grid), dim3(256), lds_rows, stream, p);
     if (Nmax > 32) hipLaunchKernelGGL(matcher_cost_kernel<4>, dim3(grid), dim3(256), 0, stream, p);
-    hipLaunchKernelGGL(matcher_finalize_kernel, dim3(cdiv((long)Q * Nmax, 256), nprob), dim3(256), 0, stream, p,
-                       class_logits, w_class, w_mask, w_dice, C);
+    if (prob0)
+        hipLaunchKernelGGL(matcher_finalize_kernel<true>, dim3(cdiv((long)Q * Nmax, 256), nprob), dim3(256), 0, stream, p,
+                           prob0, w_class, w_mask, w_dice, C);
+    else
+        hipLaunchKernelGGL(matcher_finalize_kernel<false>, dim3(cdiv((long)Q * Nmax, 256), nprob), dim3(256), 0, stream, p,
+                           class_logits, w_class, w_mask, w_dice, C);
     S2D_CHECK_LAUNCH();
     return S2D_OK;
+}
+
+extern "C" {
+
+int s2d_matcher_cost_f32(const float *mask_logits, const float *class_logits, const uint8_t *tgt, const int *tgt_count,
+                         const float *coords, uint64_t seed, int NL, int B, int Q, int ldq, int T, int hm, int wm, int H,
+                         int W, int Nmax, int P, float w_class, float w_mask, float w_dice, float *workspace, float *C,
+                         hipStream_t stream)
+{
+    return matcher_cost_impl(mask_logits, class_logits, nullptr, tgt, tgt_count, coords, seed, NL, B, Q, ldq, T, hm, wm, H, W, Nmax, P,
+                             w_class, w_mask, w_dice, workspace, C, stream);
+}
+
+long s2d_matcher_c_workspace_floats(int NL, int B, int Q, int T, int P, int H, int W)
+{
+    return s2d_matcher_workspace_floats(NL, B, T, P, H, W) + 64 + (long)NL * B * Q;
+}
+
+int s2d_matcher_cost_c_f32(const float *mask_logits, const float *class_logits, int C1, const uint8_t *tgt, const int *tgt_count,
+                           const float *coords, uint64_t seed, int NL, int B, int Q, int ldq, int T, int hm, int wm, int H,
+                           int W, int Nmax, int P, float w_class, float w_mask, float w_dice, float *workspace, float *C,
+                           hipStream_t stream)
+{
+    if (C1 < 2 || Q > QP || Q <= 0) return S2D_ERR_ARG;
+    const long rows = (long)NL * B * Q;
+    if (rows == 0) return S2D_OK;
+    float *prob0 = workspace + s2d_matcher_workspace_floats(NL, B, T, P, H, W) + 64;      // behind the cost pipeline's workspace
+    hipLaunchKernelGGL(class_prob0_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, stream, class_logits, rows, C1, prob0);
+    S2D_CHECK_LAUNCH();
+    return matcher_cost_impl(mask_logits, class_logits, prob0, tgt, tgt_count, coords, seed, NL, B, Q, ldq, T, hm, wm, H, W, Nmax, P,
+                             w_class, w_mask, w_dice, workspace, C, stream);
 }
 
 int s2d_lsap_f32(const float *C, const int *tgt_count, int nprob, int B, int Q, int Nmax, int *idx_q, int *idx_t,

@@ -25,7 +25,7 @@ def parse_args(argv=None):
     ap.add_argument("--gt", required=True, help="YTVIS annotation JSON of the split")
     ap.add_argument("--image-root", required=True, help="directory the JSON's file_names are relative to")
     ap.add_argument("--output-dir", required=True)
-    ap.add_argument("--weights", default=None, help="torch .pth (default: MODEL.WEIGHTS)")
+    ap.add_argument("--weights", default=None, help="torch .pth or detectron2 .pkl (default: MODEL.WEIGHTS)")
     ap.add_argument("--threads", type=int, default=8, help="JPEG decode threads (<= 16)")
     ap.add_argument("--prefetch", type=int, default=2, help="videos decoded ahead (1 or 2)")
     ap.add_argument("--dist-backend", default="gloo", help="process group backend under torch.distributed.run")

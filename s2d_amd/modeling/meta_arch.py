@@ -36,6 +36,29 @@ except Exception:  # detectron2 absent (as in this image): local registries with
 SEM_SEG_HEADS_REGISTRY.register(MSDeformAttnPixelDecoder)
 
 
+MAX_QUERIES = 128          # queries per clip the criterion / matcher / selection kernels take (csrc/loss.hip, matcher.hip)
+MAX_TARGETS = 128          # target slots per clip (ground truth or pseudo targets)
+MAX_CLASSES = 65535        # foreground classes: Q*C flat scores per clip stay far inside 32-bit indexing at Q = 128
+
+
+def check_class_config(cfg):
+    """refuse, as ValueError, a head configuration the kernels cannot take (rather than failing at the first launch).  Any
+    NUM_CLASSES >= 1 is supported: at 1 the class-agnostic kernels run, above 1 their class-aware forms (C + 1 logits)."""
+    C = int(cfg.MODEL.SEM_SEG_HEAD.NUM_CLASSES)
+    mf = cfg.MODEL.MASK_FORMER
+    Q = int(mf.NUM_OBJECT_QUERIES)
+    if not 1 <= C <= MAX_CLASSES:
+        raise ValueError(f"SEM_SEG_HEAD.NUM_CLASSES = {C}: supported are 1 .. {MAX_CLASSES}")
+    if not 1 <= Q <= MAX_QUERIES:
+        raise ValueError(f"MASK_FORMER.NUM_OBJECT_QUERIES = {Q}: the criterion and matcher kernels take 1 .. {MAX_QUERIES}")
+    npd = getattr(mf, "NUM_PREDICTIONS_DISTILLATION", None)
+    if C > 1 and npd is not None:
+        slots = min(int(npd), Q * C)
+        if slots > MAX_TARGETS or Q * slots > 12800:
+            raise ValueError(f"NUM_PREDICTIONS_DISTILLATION = {npd} at {C} classes gives {slots} pseudo-target slots per clip: "
+                             f"the matcher takes at most {MAX_TARGETS} (and Q * slots <= 12800)")
+
+
 @SEM_SEG_HEADS_REGISTRY.register()
 class MaskFormerHead(nn.Module):
     def __init__(self, pixel_decoder, transformer_predictor, num_classes=1):
@@ -44,9 +67,7 @@ class MaskFormerHead(nn.Module):
 
     @classmethod
     def from_config(cls, cfg, input_shape=None):  # mask_former_head.py:87-113
-        if cfg.MODEL.SEM_SEG_HEAD.NUM_CLASSES != 1:
-            raise NotImplementedError("the class-loss and matcher kernels implement the class-agnostic S2D path "
-                                      "(SEM_SEG_HEAD.NUM_CLASSES: 1 in every shipped config; labels forced to 0, matcher.py:238-243)")
+        check_class_config(cfg)
         return cls(MSDeformAttnPixelDecoder.from_config(cfg), VideoMultiScaleMaskedTransformerDecoder.from_config(
             cfg, cfg.MODEL.SEM_SEG_HEAD.CONVS_DIM, True), cfg.MODEL.SEM_SEG_HEAD.NUM_CLASSES)
 
@@ -258,35 +279,46 @@ class KDVideoMaskFormer(nn.Module):
         return _normalize_batch(batched_inputs, self.device, self.size_divisibility, self.pixel_mean.flatten().cpu().numpy(),
                                 self.pixel_std.flatten().cpu().numpy())
 
-    def _kd_nms(self, tgt, cnt, ne, kept=None):
+    def _kd_nms(self, tgt, cnt, ne, kept=None, labels=None):
         """the optional mask-NMS of prepare_distillation_targets (kd_video_maskformer_model.py:484-520): greedy over the
-        pseudo targets of a clip, a later candidate dropped when its IoU with a kept one exceeds nms_threshold (all pseudo
-        labels are the single class).  Pair counts on the device (bit-packed planes, one launch per clip), the greedy walk on
-        the K x K integers on the host -- this branch synchronises, the default path does not.  Candidate order: ascending
-        query index (the reference walks them in torch.topk(sorted=False) order, which is implementation-defined)."""
+        pseudo targets of a clip, a later candidate dropped when its IoU with a kept one of the SAME label exceeds
+        nms_threshold (labels [B,Nmax] from ops.kd_targets; None: the single class).  Pair counts on the device (bit-packed
+        planes, one launch per clip), the greedy walk on the K x K integers on the host -- this branch synchronises, the
+        default path does not.  Candidate order: ascending flat index q*C + c, i.e. ascending query index at C = 1 (the
+        reference walks them in torch.topk(sorted=False) order, which is implementation-defined)."""
         from .postprocess import greedy_mask_nms
         counts = cnt.cpu().tolist()
+        labels_h = labels.cpu().numpy() if labels is not None else None
         for b, k in enumerate(counts):
             if k < 2:
                 continue
             inter = ops.mask_pair_counts(ops.pack_mask_bits(tgt[b, :k].contiguous())).cpu().numpy()
-            keep = greedy_mask_nms(inter, [0] * k, self.nms_threshold)
+            keep = greedy_mask_nms(inter, labels_h[b, :k] if labels_h is not None else [0] * k, self.nms_threshold)
             if len(keep) < k:
                 sel = torch.as_tensor(keep, device=tgt.device, dtype=torch.long)
                 tgt[b, :len(keep)] = tgt[b, sel]
                 ne[b, :len(keep)] = ne[b, sel]
                 if kept is not None:
                     kept[b, :len(keep)] = kept[b, sel]
+                if labels is not None:
+                    labels[b, :len(keep)] = labels[b, sel]
+                    labels[b, len(keep):k] = 0
                 tgt[b, len(keep):k] = 0
                 ne[b, len(keep):k] = 0
                 cnt[b] = len(keep)
         return tgt, cnt, ne
 
+    def _kd_slots(self, class_agnostic):
+        """pseudo-target slots per clip: `class_agnostic` at NUM_CLASSES 1 (one target per query at most); with C classes the
+        flat top-K can give a query one target per label, so up to min(NUM_PREDICTIONS_DISTILLATION, Q*C)"""
+        C = self.teacher[1].num_classes
+        return class_agnostic if C == 1 else min(self.num_predictions_distillation, self.num_queries * C)
+
     @torch.no_grad()
     def forward_losses(self, images, gt_targets: TargetSet, coords_gt=None, coords_kd=None, kd_nmax=None):
         """the device-side hot path from normalised frames to the weighted loss dict (no host sync)"""
         Hp, Wp = images.shape[1:3]
-        kd_nmax = kd_nmax or min(self.num_predictions_distillation, self.num_queries)
+        kd_nmax = kd_nmax or self._kd_slots(min(self.num_predictions_distillation, self.num_queries))
         # The teacher forward (+ its pseudo-target selection) is independent of the student forward and the GT
         # criterion: it runs on a second HIP stream so the launch tails and the small decoder kernels of one network
         # fill the CUs the other leaves idle.  Every kernel is deterministic, so the schedule does not change results.
@@ -302,10 +334,10 @@ class KDVideoMaskFormer(nn.Module):
             side = main
         with torch.cuda.stream(side):
             teacher = self.teacher(images, True, aux_masks=self.teacher_aux_masks)
-            tgt, cnt, kept, ne = ops.kd_targets(teacher.class_logits[-1], teacher.mask_logits[-1], teacher.dims, Hp, Wp, kd_nmax,
-                                                self.score_threshold_distillation, self.num_predictions_distillation)
+            tgt, cnt, kept, ne, lab = ops.kd_targets(teacher.class_logits[-1], teacher.mask_logits[-1], teacher.dims, Hp, Wp, kd_nmax,
+                                                self.score_threshold_distillation, self.num_predictions_distillation, want_labels=True)
             if self.distillation_nms:
-                tgt, cnt, ne = self._kd_nms(tgt, cnt, ne, kept)
+                tgt, cnt, ne = self._kd_nms(tgt, cnt, ne, kept, lab)
         student = self.student(images, True)
         if self.overlap_teacher and self.overlap_criteria:
             side.wait_stream(main)        # student outputs ready
@@ -322,7 +354,7 @@ class KDVideoMaskFormer(nn.Module):
             losses[k.replace("loss_", "kd_loss_")] = v
         wd = self.criterion.weight_dict                                   # :319-325
         out = {k: v * wd[k] for k, v in losses.items() if k in wd}
-        self.last = dict(student=student, teacher=teacher, kd_count=cnt, kd_kept=kept)
+        self.last = dict(student=student, teacher=teacher, kd_count=cnt, kd_kept=kept, kd_labels=lab)
         if getattr(self, "keep_kd_targets", False):       # tests: the pseudo-target planes the KD matcher saw (1.5 GB at c4 otherwise freed)
             self.last["kd_targets"] = tgt
         return out
@@ -386,10 +418,11 @@ class KDVideoMaskFormer(nn.Module):
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
                     teacher = self.teacher(img, True, aux_masks=self.teacher_aux_masks)
-                    tgt, cnt, kept, ne = ops.kd_targets(teacher.class_logits[-1], teacher.mask_logits[-1], teacher.dims, Hp, Wp, kd_nmax,
-                                                        self.score_threshold_distillation, self.num_predictions_distillation)
+                    tgt, cnt, kept, ne, lab = ops.kd_targets(teacher.class_logits[-1], teacher.mask_logits[-1], teacher.dims, Hp, Wp,
+                                                             kd_nmax, self.score_threshold_distillation, self.num_predictions_distillation,
+                                                             want_labels=True)
                     if self.distillation_nms:
-                        tgt, cnt, ne = self._kd_nms(tgt, cnt, ne, kept)
+                        tgt, cnt, ne = self._kd_nms(tgt, cnt, ne, kept, lab)
                 student = self.student(img, True)
                 crit.wait_stream(main); crit.wait_stream(side)
                 gt_b = TargetSet(gt_targets.masks[b:b + 1], gt_targets.count[b:b + 1], gt_targets.nonempty[b:b + 1], [ns[b]])
@@ -451,7 +484,7 @@ class KDVideoMaskFormer(nn.Module):
         overlapped gradient all-reduce hangs on (optim.OverlappedAllReduce; DDP's bucket hooks in the reference)."""
         wd = self.criterion.weight_dict
         Hp, Wp = images.shape[1:3]
-        kd_nmax = kd_nmax or self.num_queries
+        kd_nmax = kd_nmax or self._kd_slots(self.num_queries)
         backbone, head = self.student[0], self.student[1]
         tb, tp, td = [], [], []
         main = torch.cuda.current_stream(images.device)
@@ -464,10 +497,10 @@ class KDVideoMaskFormer(nn.Module):
             side = main
         with torch.cuda.stream(side):
             teacher = self.teacher(images, True, aux_masks=self.teacher_aux_masks)
-            tgt, cnt, kept, ne = ops.kd_targets(teacher.class_logits[-1], teacher.mask_logits[-1], teacher.dims, Hp, Wp, kd_nmax,
-                                                self.score_threshold_distillation, self.num_predictions_distillation)
+            tgt, cnt, kept, ne, lab = ops.kd_targets(teacher.class_logits[-1], teacher.mask_logits[-1], teacher.dims, Hp, Wp, kd_nmax,
+                                                self.score_threshold_distillation, self.num_predictions_distillation, want_labels=True)
             if self.distillation_nms:
-                tgt, cnt, ne = self._kd_nms(tgt, cnt, ne, kept)
+                tgt, cnt, ne = self._kd_nms(tgt, cnt, ne, kept, lab)
         feats = backbone(images, tb)
         mf, ms = head.pixel_decoder.forward_features(feats, tp)
         student = head.predictor(ms, mf, True, True, td)
@@ -549,7 +582,7 @@ class KDVideoMaskFormer(nn.Module):
                 Bk.scale_grads([p for n in scaled for p in parts[n]], 1.0 / S)
         if grad_ready is not None:
             grad_ready("backbone")
-        self.last = dict(student=student, teacher=teacher, kd_count=cnt, kd_kept=kept)
+        self.last = dict(student=student, teacher=teacher, kd_count=cnt, kd_kept=kept, kd_labels=lab)
         # the activation tapes are garbage once the gradients exist; keeping them alive into the next iteration's forward
         # costs 45 GiB of peak memory at c4 (keep_tapes = True for tests that inspect them)
         self.last_tapes = (tb, tp, td) if getattr(self, "keep_tapes", False) else None

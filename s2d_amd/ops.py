@@ -647,18 +647,26 @@ def masked_attn(q, k, v, bits=None, unmasked=None, H=8, want_lse=False):
 
 # ----------------------------------------------------------------------------- matcher / criterion
 def matcher_cost(mask_logits, class_logits, tgt, tgt_count, dims, P, weights, coords=None, seed=0):
-    """mask_logits [NL,B,T*hm*wm,ldq] pixel-major, class_logits [NL,B,Q,2], tgt u8 [B,Nmax,T,H,W], tgt_count i32 [B].
-    dims = (Q, T, hm, wm).  -> C [NL*B, Q, Nmax]"""
+    """mask_logits [NL,B,T*hm*wm,ldq] pixel-major, class_logits [NL,B,Q,C1] (C1 = classes + 1), tgt u8 [B,Nmax,T,H,W],
+    tgt_count i32 [B].  dims = (Q, T, hm, wm).  -> C [NL*B, Q, Nmax]"""
     _chk(mask_logits); _chk(class_logits); _chk(tgt, torch.uint8); _chk(tgt_count, torch.int32); _chk(coords)
     NL, B = mask_logits.shape[:2]
     Q, T, hm, wm = dims
+    C1 = class_logits.shape[-1]
     Nmax, H, W = tgt.shape[1], tgt.shape[3], tgt.shape[4]
-    n = lib().call("s2d_matcher_workspace_floats", NL, B, T, int(P), H, W)
+    if C1 > 2:
+        n = lib().call("s2d_matcher_c_workspace_floats", NL, B, Q, T, int(P), H, W)
+    else:
+        n = lib().call("s2d_matcher_workspace_floats", NL, B, T, int(P), H, W)
     ws = torch.empty((n,), device=tgt.device, dtype=torch.float32)
     C = torch.empty((NL * B, Q, Nmax), device=tgt.device, dtype=torch.float32)
     wc, wm_, wd = weights
-    lib().call("s2d_matcher_cost_f32", mask_logits, class_logits, tgt, tgt_count, coords, int(seed), NL, B, Q,
-               mask_logits.shape[-1], T, hm, wm, H, W, Nmax, P, float(wc), float(wm_), float(wd), ws, C, _stream())
+    rest = (tgt, tgt_count, coords, int(seed), NL, B, Q, mask_logits.shape[-1], T, hm, wm, H, W, Nmax, P, float(wc), float(wm_),
+            float(wd), ws, C, _stream())
+    if C1 > 2:
+        lib().call("s2d_matcher_cost_c_f32", mask_logits, class_logits, C1, *rest)
+    else:
+        lib().call("s2d_matcher_cost_f32", mask_logits, class_logits, *rest)
     return C
 
 
@@ -674,19 +682,28 @@ def lsap(C, tgt_count, B):
     return iq, it, nm
 
 
-def kd_targets(t_class_logits, t_mask_logits, dims, H, W, Nmax, thr=0.75, topk=100):
-    """teacher class logits [B,Q,2], mask logits pixel-major [B,T*hm*wm,ldq]; dims=(Q,T,hm,wm)."""
+def kd_targets(t_class_logits, t_mask_logits, dims, H, W, Nmax, thr=0.75, topk=100, want_labels=False):
+    """teacher class logits [B,Q,C1], mask logits pixel-major [B,T*hm*wm,ldq]; dims=(Q,T,hm,wm).
+    -> tgt, count, kept (query of each pseudo target), nonempty (+ the label of each pseudo target with want_labels:
+    None at C1 = 2, where every label is 0).
+    C1 > 2 selects over the flattened [Q*C] scores, so one query may give a target per label (ascending q*C + c order)."""
     _chk(t_class_logits); _chk(t_mask_logits)
-    B = t_class_logits.shape[0]
+    B, _, C1 = t_class_logits.shape
     Q, T, hm, wm = dims
     dev = t_class_logits.device
     tgt = torch.empty((B, Nmax, T, H, W), device=dev, dtype=torch.uint8)
     count = torch.zeros((B,), device=dev, dtype=torch.int32)
     kept = torch.zeros((B, Nmax), device=dev, dtype=torch.int32)
+    label = torch.zeros((B, Nmax), device=dev, dtype=torch.int32) if C1 > 2 else None
     nonempty = torch.empty((B, Nmax, T), device=dev, dtype=torch.int32)
-    lib().call("s2d_kd_targets_u8", t_class_logits, t_mask_logits, float(thr), int(topk), B, Q, t_mask_logits.shape[-1], T, hm,
-               wm, H, W, Nmax, tgt, count, kept, nonempty, _stream())
-    return tgt, count, kept, nonempty
+    if C1 > 2:
+        ws = torch.empty((lib().call("s2d_kd_targets_c_workspace_bytes", B, Q, C1),), device=dev, dtype=torch.uint8)
+        lib().call("s2d_kd_targets_c_u8", t_class_logits, C1, t_mask_logits, float(thr), int(topk), B, Q, t_mask_logits.shape[-1], T,
+                   hm, wm, H, W, Nmax, ws, tgt, count, kept, label, nonempty, _stream())
+    else:
+        lib().call("s2d_kd_targets_u8", t_class_logits, t_mask_logits, float(thr), int(topk), B, Q, t_mask_logits.shape[-1], T, hm,
+                   wm, H, W, Nmax, tgt, count, kept, nonempty, _stream())
+    return (tgt, count, kept, nonempty, label) if want_labels else (tgt, count, kept, nonempty)
 
 
 def target_nonempty(tgt, count):
@@ -741,33 +758,49 @@ def point_loss_backward(ctx, w_mask, w_dice):
 
 
 def class_loss_backward(class_logits, idx_q, n_match, w_ce, eos_coef=0.1):
-    """d(w_ce * loss_ce)/d(class_logits [B,Q,2])"""
+    """d(w_ce * loss_ce)/d(class_logits [B,Q,C1])"""
     _chk(class_logits); _chk(idx_q, torch.int32); _chk(n_match, torch.int32)
-    B, Q, _ = class_logits.shape
+    B, Q, C1 = class_logits.shape
     out = torch.empty_like(class_logits)
-    lib().call("s2d_class_loss_backward_f32", class_logits, idx_q, n_match, B, Q, idx_q.shape[-1], float(eos_coef), float(w_ce), out, _stream())
+    if C1 > 2:
+        lib().call("s2d_class_loss_backward_c_f32", class_logits, C1, idx_q, n_match, B, Q, idx_q.shape[-1], float(eos_coef), float(w_ce),
+                   out, _stream())
+    else:
+        lib().call("s2d_class_loss_backward_f32", class_logits, idx_q, n_match, B, Q, idx_q.shape[-1], float(eos_coef), float(w_ce), out,
+                   _stream())
     return out
 
 
 def class_loss(class_logits, idx_q, n_match, eos_coef=0.1):
-    """class_logits [B,Q,2], idx_q [B,maxm], n_match [B] -> 0-dim loss_ce"""
+    """class_logits [B,Q,C1], idx_q [B,maxm], n_match [B] -> 0-dim loss_ce (matched -> class 0, others -> no object C1 - 1)"""
     _chk(class_logits); _chk(idx_q, torch.int32); _chk(n_match, torch.int32)
-    B, Q, _ = class_logits.shape
+    B, Q, C1 = class_logits.shape
     out = torch.zeros((1,), device=class_logits.device, dtype=torch.float32)
-    lib().call("s2d_class_loss_f32", class_logits, idx_q, n_match, B, Q, idx_q.shape[-1], float(eos_coef), out, _stream())
+    if C1 > 2:
+        lib().call("s2d_class_loss_c_f32", class_logits, C1, idx_q, n_match, B, Q, idx_q.shape[-1], float(eos_coef), out, _stream())
+    else:
+        lib().call("s2d_class_loss_f32", class_logits, idx_q, n_match, B, Q, idx_q.shape[-1], float(eos_coef), out, _stream())
     return out[0]
 
 
 # --------------------------------------------------------------------------- eval-side post-processing (infer.hip)
+INFER_SELECT_LDS_SCORES = 16384       # Q*C scores s2d_infer_select_f32 holds in its 64 KB of LDS
+
+
 def infer_select(class_logits, K):
-    """class_logits [Q,C+1] -> (scores [K] f32, query [K] i32, label [K] i32): softmax[:, :-1], sorted top-K"""
+    """class_logits [Q,C+1] -> (scores [K] f32, query [K] i32, label [K] i32): softmax[:, :-1], sorted top-K (equal scores:
+    lower flat index q*C + c first).  Up to 16384 scores one workgroup ranks them in LDS; beyond, the multi-workgroup form."""
     _chk(class_logits)
     Q, C1 = class_logits.shape
     dev = class_logits.device
     scores = torch.empty((K,), device=dev, dtype=torch.float32)
     query = torch.empty((K,), device=dev, dtype=torch.int32)
     label = torch.empty((K,), device=dev, dtype=torch.int32)
-    lib().call("s2d_infer_select_f32", class_logits, Q, C1 - 1, K, scores, query, label, _stream())
+    if Q * (C1 - 1) > INFER_SELECT_LDS_SCORES:
+        ws = torch.empty((lib().call("s2d_infer_select_c_workspace_bytes", Q, C1),), device=dev, dtype=torch.uint8)
+        lib().call("s2d_infer_select_c_f32", class_logits, Q, C1, K, ws, scores, query, label, _stream())
+    else:
+        lib().call("s2d_infer_select_f32", class_logits, Q, C1 - 1, K, scores, query, label, _stream())
     return scores, query, label
 
 

@@ -50,7 +50,7 @@ def parse_args(argv=None):
     ap.add_argument("--train-json", required=True, help="YTVIS annotation JSON to train on (ground truth or pseudo labels)")
     ap.add_argument("--image-root", required=True, help="directory the JSON's file_names are relative to")
     ap.add_argument("--output-dir", required=True)
-    ap.add_argument("--weights", default=None, help="initial weights, torch .pth (default: MODEL.WEIGHTS)")
+    ap.add_argument("--weights", default=None, help="initial weights, torch .pth or detectron2 .pkl (default: MODEL.WEIGHTS)")
     ap.add_argument("--resume", action="store_true", help="continue from OUTPUT_DIR/last_checkpoint")
     ap.add_argument("--eval-gt", default=None, help="YTVIS annotation JSON to score on (EvalHook)")
     ap.add_argument("--eval-image-root", default=None)
