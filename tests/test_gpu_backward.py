@@ -488,6 +488,18 @@ def test_pixel_decoder_backward_vs_autograd(p_drop):
     assert not bad, bad
 
 
+def _masked_attn_torch(q, k, v, mask, H=8):
+    """the attention core in plain torch (any dtype / device): softmax(q k^T / sqrt(d) with `mask`ed keys at -inf) v per head; a query
+    with every key masked attends everywhere (video_mask2former_transformer_decoder.py:413)"""
+    B, Q, C = q.shape
+    K, D = k.shape[1], C // H
+    eff = mask.clone()
+    eff[eff.all(-1)] = False
+    sc = torch.einsum("bqhd,bkhd->bhqk", q.reshape(B, Q, H, D), k.reshape(B, K, H, D)) / D ** 0.5
+    sc = sc.masked_fill(eff[:, None], float("-inf"))
+    return torch.einsum("bhqk,bkhd->bqhd", torch.softmax(sc, -1), v.reshape(B, K, H, D)).reshape(B, Q, C)
+
+
 @pytest.mark.parametrize("B,Q,K,masked", [(2, 100, 1500, True), (1, 100, 100, False), (2, 37, 333, True), (1, 100, 20000, True)])
 def test_masked_attention_backward_vs_autograd(B, Q, K, masked):
     """decoder attention core (nn.MultiheadAttention after the in-projections, video_mask2former_transformer_decoder.py:41-51,
@@ -501,11 +513,7 @@ def test_masked_attention_backward_vs_autograd(B, Q, K, masked):
     if masked:
         mask[0, 3] = True                                            # a query with every key masked attends everywhere
     qd, kd, vd = (t.double().requires_grad_(True) for t in (q, k, v))
-    eff = mask.clone()
-    eff[eff.all(-1)] = False
-    sc = torch.einsum("bqhd,bkhd->bhqk", qd.view(B, Q, H, 32), kd.view(B, K, H, 32)) / 32 ** 0.5
-    sc = sc.masked_fill(eff[:, None], float("-inf"))
-    out = torch.einsum("bhqk,bkhd->bqhd", torch.softmax(sc, -1), vd.view(B, K, H, 32)).reshape(B, Q, C)
+    out = _masked_attn_torch(qd, kd, vd, mask, H)
     (out * dout.double()).sum().backward()
     bits = unm = None
     if masked:

@@ -195,7 +195,8 @@ def test_bench_plain_run_is_lean_and_full_run_adds_the_reports(tmp_path):
 
 
 def test_train_step_at_config4_gradients_finite_and_reproducible(setup):
-    """BASELINE configs[3]'s training leg at full size (no autograd oracle fits there): every one of the 345 student gradients
+    """BASELINE configs[3]'s training leg at full size (the whole iteration has no autograd oracle that fits there; each backward kernel
+    call it makes is compared with float64 at these shapes in tests/test_gpu_backward_c4.py): every one of the 345 student gradients
     is finite, and two iterations on the same batch with the same seeds agree bit for bit (no float atomics are left in the step:
     MSDeformAttn's grad_value is a sorted gather, the point-loss scatter accumulates in fixed point)"""
     from s2d_amd import ops
