@@ -794,6 +794,22 @@ int s2d_mask_frame_areas_i32(const uint8_t *masks, int K, int T, int H, int W, i
 int s2d_render_instances_u8(const uint8_t *frames, int T, int H, int W, const uint8_t *masks, int K, const int *order,
                             const uint8_t *colors, int alpha, uint8_t *overlay, uint8_t *index, hipStream_t stream);
 
+/* ---- windowed inference of long videos (s2d_amd/modeling/window_inference.py) ------------------------------ */
+
+/* Cross-window mask counts from two pixel-major fp32 logit blocks A, B [n][ldq] (the frames two consecutive windows share, n =
+ * O*hm*wm rows): with a_i = (A[:, i] > 0) and b_j = (B[:, j] > 0) for the Q query columns (so -0.0, 0.0 and NaN are outside the
+ * mask), inter [Q][Q] = |a_i & b_j|, area_a [Q] = |a_i|, area_b [Q] = |b_j|, all int64 and zeroed by the call.  The pad columns
+ * Q .. ldq-1 may hold anything.  No planes or byte masks are written: the blocks are read once.  Q <= ldq <= 128, ldq a multiple
+ * of 4, A and B 16-byte aligned, n < 2^31. */
+int s2d_window_pair_counts(const float *A, const float *B, long n, int ldq, int Q, int64_t *inter, int64_t *area_a,
+                           int64_t *area_b, hipStream_t stream);
+
+/* dst[row0 + r][p] = src[r][perm[p]] for r < rows and p < Q; the pad columns Q <= p < ldq are copied as they are.  src [rows][ldq],
+ * dst [>= row0 + rows][ldq] 16-byte aligned, perm DEVICE int32 [Q] (an entry outside [0, Q) reads column p itself).  A window's
+ * owned rows go into the stitched buffer in track order in one pass.  Q <= ldq <= 128, ldq a multiple of 4. */
+int s2d_window_scatter_columns(const float *src, long rows, int ldq, int Q, const int *perm, float *dst, long row0,
+                               hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

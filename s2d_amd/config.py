@@ -38,7 +38,9 @@ DEFAULTS = {
             "EMA_MOMENTUM": 0.999, "EMA_MOMENTUM_SCHEDULE": False, "EMA_MOMENTUM_END": 0.999, "EMA_MOMENTUM_UNTIL_STEP": 10000,
             "TEST": {"SEMANTIC_ON": True, "INSTANCE_ON": False, "PANOPTIC_ON": False, "OBJECT_MASK_THRESHOLD": 0.0,
                      "OVERLAP_THRESHOLD": 0.0, "SEM_SEG_POSTPROCESSING_BEFORE_INFERENCE": False, "USE_NMS": False,
-                     "NMS_THRESH": 0.6, "NUM_PREDICTIONS": 10, "EVAL_STUDENT": False},
+                     "NMS_THRESH": 0.6, "NUM_PREDICTIONS": 10, "EVAL_STUDENT": False,
+                     # this library's own keys (no reference counterpart): windowed inference of long videos, DESIGN.md section 1
+                     "WINDOW_INFERENCE": False, "WINDOW_SIZE": 0, "WINDOW_OVERLAP": 0},
         },
     },
     "INPUT": {

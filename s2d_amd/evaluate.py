@@ -7,8 +7,9 @@ key conversions (checkpoint.load_checkpoint; every tensor of the evaluated netwo
 split through `model([inputs])` with the test loader (data/test_loader.py) and YTVISEvaluator.process.  Predictions stay on the
 device until they are COCO RLE (the meta-arch's inference_rle switch); labels map to the GT file's category ids in sorted order, as
 the registered dataset's metadata maps them.  Writes OUT/results.json (the reference layout),
-OUT/metrics.json (the "segm" dict; not for a split without annotations) and prints one JSON timing line: videos/s, frames/s and
-the fraction of the wall time the model waited on the loader.  Under torch.distributed.run the videos are split round-robin by
+OUT/metrics.json (the "segm" dict; not for a split without annotations) and prints one JSON timing line: videos/s, frames/s, the
+number of windows run (one per video unless MODEL.MASK_FORMER.TEST.WINDOW_INFERENCE cuts long videos) and the fraction of the wall
+time the model waited on the loader.  Under torch.distributed.run the videos are split round-robin by
 rank and rank 0 writes the files."""
 import argparse
 import json
@@ -69,7 +70,7 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
     was_training, was_rle = model.training, getattr(model, "inference_rle", False)
     model.eval()
     model.inference_rle = True
-    nvid = nfr = 0
+    nvid = nfr = nwin = 0
     try:
         torch.cuda.synchronize(device)
         t0 = time.perf_counter()
@@ -79,6 +80,7 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
                 evaluator.process([inputs], outputs)
                 nvid += 1
                 nfr += len(inputs["image"])
+                nwin += getattr(model, "last_windows", 1)
         torch.cuda.synchronize(device)
         wall = time.perf_counter() - t0
     finally:
@@ -91,7 +93,7 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
         if "segm" in results:
             with open(os.path.join(output_dir, "metrics.json"), "w") as fh:
                 json.dump(results["segm"], fh)
-    line = {"rank": rank, "videos": nvid, "frames": nfr, "wall_s": round(wall, 4),
+    line = {"rank": rank, "videos": nvid, "frames": nfr, "windows": nwin, "wall_s": round(wall, 4),
             "videos_per_s": round(nvid / wall, 4) if wall > 0 else None,
             "frames_per_s": round(nfr / wall, 3) if wall > 0 else None,
             "loader_wait_fraction": round(loader.wait_s / wall, 4) if wall > 0 else None}

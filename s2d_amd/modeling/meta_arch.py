@@ -17,6 +17,7 @@ from .criterion import TargetSet, VideoHungarianMatcher, VideoSetCriterion
 from .pixel_decoder import MSDeformAttnPixelDecoder
 from .postprocess import inference_video
 from .video_decoder import VideoMultiScaleMaskedTransformerDecoder
+from .window_inference import check_window_config, run_windows, window_kwargs
 
 try:  # plug into detectron2's registries when it is installed (the drop-in boundary)
     from detectron2.modeling import META_ARCH_REGISTRY, SEM_SEG_HEADS_REGISTRY  # type: ignore
@@ -207,8 +208,10 @@ class KDVideoMaskFormer(nn.Module):
     def __init__(self, *, student_backbone, student_sem_seg_head, teacher_backbone, teacher_sem_seg_head, criterion,
                  num_queries, num_frames, size_divisibility=32, pixel_mean=ops.PIXEL_MEAN, pixel_std=ops.PIXEL_STD,
                  num_predictions_distillation=100, score_threshold_distillation=0.75, accum_iter=1, eval_student=False,
-                 use_nms=False, nms_threshold=0.75, num_predictions_inference=10, distillation_nms=False):
+                 use_nms=False, nms_threshold=0.75, num_predictions_inference=10, distillation_nms=False,
+                 window_inference=False, window_size=0, window_overlap=0):
         super().__init__()
+        check_window_config(window_inference, window_size, window_overlap, num_queries)
         self.student = _Net(student_backbone, student_sem_seg_head)
         self.teacher = _Net(teacher_backbone, teacher_sem_seg_head)
         for p in self.teacher.parameters():
@@ -222,6 +225,9 @@ class KDVideoMaskFormer(nn.Module):
         self.accum_iter, self.eval_student = accum_iter, eval_student
         self.use_nms, self.nms_threshold, self.num_predictions_inference = use_nms, nms_threshold, num_predictions_inference
         self.distillation_nms = distillation_nms          # MODEL.MASK_FORMER.DISTILLATION_NMS (off in every shipped config)
+        # MODEL.MASK_FORMER.TEST.WINDOW_*: eval branch on windows of frames, tracks stitched on the device (window_inference.py)
+        self.window_inference, self.window_size, self.window_overlap = bool(window_inference), int(window_size), int(window_overlap)
+        self.last_windows = 0                       # windows the last eval-mode call ran (1: the one-clip path)
         # Optional two-stream schedule of forward_losses (teacher forward / GT criterion on a second HIP stream): ~8 % faster
         # and bitwise identical to the one-stream schedule (bench.py re-checks that on every run; DESIGN.md section 5,
         # "Streams", has the history of why the default here stays one stream).
@@ -245,6 +251,7 @@ class KDVideoMaskFormer(nn.Module):
     @classmethod
     def from_config(cls, cfg):  # kd_video_maskformer_model.py:130-231
         mf = cfg.MODEL.MASK_FORMER
+        wkw = window_kwargs(mf)                     # refused before anything is built
         sb, tb = ResNet50(), ResNet50()
         sh, th = MaskFormerHead.from_config(cfg), MaskFormerHead.from_config(cfg)
         cw, dw, mw = mf.CLASS_WEIGHT, mf.DICE_WEIGHT, mf.MASK_WEIGHT
@@ -269,7 +276,7 @@ class KDVideoMaskFormer(nn.Module):
                    num_predictions_distillation=mf.NUM_PREDICTIONS_DISTILLATION,
                    score_threshold_distillation=mf.SCORE_THRESHOLD_DISTILLATION, accum_iter=cfg.SOLVER.ACCUM_ITER,
                    distillation_nms=bool(getattr(mf, "DISTILLATION_NMS", False)),
-                   **_test_kwargs(mf, "num_predictions_inference", eval_student=True))
+                   **_test_kwargs(mf, "num_predictions_inference", eval_student=True), **wkw)
 
     @property
     def device(self):
@@ -611,16 +618,32 @@ class KDVideoMaskFormer(nn.Module):
         pred_labels, pred_masks}."""
         net = self.student if self.eval_student else self.teacher
         return _inference(net, images, batched_inputs, self.num_predictions_inference, self.use_nms, self.nms_threshold,
-                          rle=getattr(self, "inference_rle", False), device_masks=getattr(self, "inference_device_masks", False))
+                          rle=getattr(self, "inference_rle", False), device_masks=getattr(self, "inference_device_masks", False),
+                          window=self._window(), owner=self)
+
+    def _window(self):
+        return (self.window_size, self.window_overlap) if self.window_inference else None
 
 
-def _inference(net, images, batched_inputs, num_predictions, use_nms, nms_threshold, rle=False, device_masks=False):
-    out = net(images, False)
+def _inference(net, images, batched_inputs, num_predictions, use_nms, nms_threshold, rle=False, device_masks=False, window=None,
+               owner=None):
+    """window = (W, O): a video of more than W frames runs window by window and is stitched (window_inference.run_windows); one of
+    at most W frames, or window = None, is the one-clip path.  owner.last_windows receives the number of windows run."""
     video = batched_inputs[0]
+    if owner is not None:
+        owner.last_windows = 1
+    if window is not None and images.shape[0] > window[0]:
+        cls, ml, dims, nwin = run_windows(net, images, window[0], window[1])
+        if owner is not None:
+            owner.last_windows = nwin
+    else:
+        out = net(images, False)
+        cls, ml, dims = out.class_logits[-1][0], out.mask_logits[-1][0], (out.T, out.hm, out.wm)
+        del out
     first = video["image"][0]
     image_size = tuple(int(v) for v in first.shape[-2:])            # size without padding (images.image_sizes[0], :349)
     height, width = video.get("height", image_size[0]), video.get("width", image_size[1])   # :351-352
-    return inference_video(out.class_logits[-1][0], out.mask_logits[-1][0], (out.T, out.hm, out.wm), tuple(images.shape[1:3]),
+    return inference_video(cls, ml, dims, tuple(images.shape[1:3]),
                            image_size, (int(height), int(width)), num_predictions, use_nms, nms_threshold, rle=rle,
                            device_masks=device_masks)
 
@@ -630,8 +653,10 @@ class VideoMaskFormer(nn.Module):
     """Non-KD variant (video_maskformer_model.py:189-265): one network, one criterion pass."""
 
     def __init__(self, *, backbone, sem_seg_head, criterion, num_queries, num_frames, size_divisibility=32,
-                 pixel_mean=ops.PIXEL_MEAN, pixel_std=ops.PIXEL_STD, use_nms=False, nms_threshold=0.75, num_predictions=10):
+                 pixel_mean=ops.PIXEL_MEAN, pixel_std=ops.PIXEL_STD, use_nms=False, nms_threshold=0.75, num_predictions=10,
+                 window_inference=False, window_size=0, window_overlap=0):
         super().__init__()
+        check_window_config(window_inference, window_size, window_overlap, num_queries)
         self.backbone, self.sem_seg_head, self.criterion = backbone, sem_seg_head, criterion
         self.num_queries, self.num_frames, self.size_divisibility = num_queries, num_frames, size_divisibility
         self.use_nms, self.nms_threshold, self.num_predictions = use_nms, nms_threshold, num_predictions
@@ -639,12 +664,15 @@ class VideoMaskFormer(nn.Module):
         self.register_buffer("pixel_std", torch.tensor(pixel_std, dtype=torch.float32).view(-1, 1, 1), False)
         self.inference_rle = False                  # see KDVideoMaskFormer
         self.inference_device_masks = False
+        self.window_inference, self.window_size, self.window_overlap = bool(window_inference), int(window_size), int(window_overlap)
+        self.last_windows = 0
 
     @classmethod
     def from_config(cls, cfg):  # video_maskformer_model.py:97-187 (the sparse-class / entropy / DropLoss variants are not on the path)
         mf = cfg.MODEL.MASK_FORMER
         if getattr(mf, "SPARSE_CLASS_WEIGHT", 0.0) > 0.0 or getattr(mf, "MASK_DROPLOSS", False) or getattr(mf, "LABEL_DROPLOSS", False):
             raise NotImplementedError("SPARSE_CLASS_WEIGHT / MASK_DROPLOSS / LABEL_DROPLOSS criterion variants")
+        wkw = window_kwargs(mf)
         head = MaskFormerHead.from_config(cfg)
         cw, dw, mw = mf.CLASS_WEIGHT, mf.DICE_WEIGHT, mf.MASK_WEIGHT
         matcher = VideoHungarianMatcher(0.0 if getattr(mf, "NO_CLASS_MATCH", False) else cw, mw, dw, mf.TRAIN_NUM_POINTS)
@@ -659,7 +687,7 @@ class VideoMaskFormer(nn.Module):
                                  importance_sample_ratio=mf.IMPORTANCE_SAMPLE_RATIO, loss_strategy=mf.LOSS_STRATEGY)
         m = cls(backbone=ResNet50(), sem_seg_head=head, criterion=crit, num_queries=mf.NUM_OBJECT_QUERIES,
                 num_frames=cfg.INPUT.SAMPLING_FRAME_NUM, size_divisibility=mf.SIZE_DIVISIBILITY, pixel_mean=cfg.MODEL.PIXEL_MEAN,
-                pixel_std=cfg.MODEL.PIXEL_STD, **_test_kwargs(mf, "num_predictions"))
+                pixel_std=cfg.MODEL.PIXEL_STD, **_test_kwargs(mf, "num_predictions"), **wkw)
         m.accum_iter = cfg.SOLVER.ACCUM_ITER
         return m
 
@@ -723,7 +751,8 @@ class VideoMaskFormer(nn.Module):
             with torch.no_grad():
                 return _inference(net, images, batched_inputs, self.num_predictions, self.use_nms, self.nms_threshold,
                                   rle=getattr(self, "inference_rle", False),
-                                  device_masks=getattr(self, "inference_device_masks", False))
+                                  device_masks=getattr(self, "inference_device_masks", False),
+                                  window=(self.window_size, self.window_overlap) if self.window_inference else None, owner=self)
         Hp, Wp = images.shape[1:3]
         gt = TargetSet.from_list(_gt_target_list(batched_inputs, self.num_frames, Hp, Wp, self.device), device=self.device)
         params = [p for p in list(self.backbone.parameters()) + list(self.sem_seg_head.parameters()) if p.requires_grad]

@@ -839,6 +839,33 @@ def mask_pair_counts(bits):
     return inter
 
 
+# --------------------------------------------------------------------------- windowed inference (window.hip)
+def window_pair_counts(a, b, Q):
+    """pixel-major logit blocks a, b [n, ldq] of the same frames in two windows -> (inter [Q,Q], area_a [Q], area_b [Q]) int64:
+    the counts of the masks `logit > 0` of every query pair, read straight from the logits"""
+    _chk(a); _chk(b)
+    if a.dim() != 2 or a.shape != b.shape or not 1 <= Q <= a.shape[1]:
+        raise ValueError(f"window_pair_counts needs two [n, ldq] blocks of one shape and 1 <= Q <= ldq, got {tuple(a.shape)}, "
+                         f"{tuple(b.shape)}, Q = {Q}")
+    n, ldq = a.shape
+    inter = torch.empty((Q, Q), device=a.device, dtype=torch.int64)
+    area_a = torch.empty((Q,), device=a.device, dtype=torch.int64)
+    area_b = torch.empty((Q,), device=a.device, dtype=torch.int64)
+    lib().call("s2d_window_pair_counts", a, b, n, ldq, Q, inter, area_a, area_b, _stream())
+    return inter, area_a, area_b
+
+
+def window_scatter_columns(src, perm, dst, row0, Q):
+    """dst[row0 + r, p] = src[r, perm[p]] for the Q query columns (pad columns copied as they are); src [rows, ldq], dst
+    [R, ldq] with row0 + rows <= R, perm int32 [Q] on the device.  Writes into dst, returns nothing."""
+    _chk(src); _chk(dst); _chk(perm, torch.int32)
+    rows, ldq = src.shape
+    if dst.dim() != 2 or dst.shape[1] != ldq or row0 < 0 or row0 + rows > dst.shape[0] or perm.numel() != Q or not 1 <= Q <= ldq:
+        raise ValueError(f"window_scatter_columns: src {tuple(src.shape)} at row {row0} of dst {tuple(dst.shape)}, perm "
+                         f"{tuple(perm.shape)}, Q = {Q}")
+    lib().call("s2d_window_scatter_columns", src, rows, ldq, Q, perm, dst, row0, _stream())
+
+
 def mask_frame_areas(masks, want_order=True):
     """u8 masks [K,T,H,W] (the infer_masks layout) -> (areas int32 [K,T], draw order int32 [T,K] or None): per frame the instances
     by descending area, ties in instance order.  K <= 255."""
