@@ -192,3 +192,118 @@ def test_msda_backward_sorted_is_reproducible_and_matches_the_atomic_form():
         assert torch.equal(x, y), name
         scale = float(z.abs().max())
         assert float((x - z).abs().max()) <= 2e-5 * scale, name
+
+
+# --------------------------------------------------------------------------- both sides of the element-wise kernels' size thresholds
+def _rel64(got, ref):
+    """`rel` of tests/test_gpu_backward.py on device tensors: max abs error / max abs reference"""
+    return float((got.double() - ref).abs().max()) / max(float(ref.abs().max()), 1e-30)
+
+
+def _groupnorm64(x, G, ga, be, up=None, relu=False, dt=torch.float64):
+    """float64 GroupNorm (+ bilinear `up`, ReLU) of an NHWC float32 tensor, in plain torch on the device"""
+    F = torch.nn.functional
+    y = F.group_norm(x.to(dt).permute(0, 3, 1, 2), G, ga.to(dt), be.to(dt), 1e-5)
+    if up is not None:
+        y = y + F.interpolate(up.to(dt).permute(0, 3, 1, 2), size=tuple(x.shape[1:3]), mode="bilinear", align_corners=False)
+    y = y.permute(0, 2, 3, 1)
+    return torch.relu(y) if relu else y
+
+
+# HW = 257 / 258: two row blocks of gn_stats_kernel (256 rows each at HW <= 61 440), the last one ragged with 1 / 2 rows;
+# 62 x 1000 = 62 000 = 4 k: rows_per_blk = 259, 240 blocks, last block 99 rows, gn_reduce_kernel lanes with 3 and 4 partials;
+# N * HW * C / 4 around 2^20 at C = 256 and N = 4: HW = 4096 (exactly 2^20, gn_apply_px_kernel), 4092 (HW % 4 == 0 just below, gn_apply_kernel),
+# 4094 and 4102 (HW % 4 == 2 just below and just above: gn_apply_kernel on both sides); C = 64 and C = 1024 on both sides as well
+_GN_CASES = [(2, 1, 257, 256, None), (2, 129, 2, 256, None), (1, 62, 1000, 256, (31, 500)), (4, 64, 64, 256, (32, 32)), (4, 62, 66, 256, None),
+             (4, 46, 89, 256, None), (4, 2, 2051, 256, (1, 1025)), (2, 46, 45, 256, (23, 45)), (3, 45, 46, 256, (23, 23)),
+             (16, 64, 64, 64, (32, 32)), (15, 64, 64, 64, None), (1, 64, 64, 1024, (32, 32)), (1, 62, 66, 1024, None), (1, 3, 86, 1024, None)]
+
+
+@pytest.mark.parametrize("N,H,W,C,up_hw", _GN_CASES)
+def test_groupnorm_both_sides_of_the_size_thresholds(N, H, W, C, up_hw):
+    """groupnorm_nhwc against float64 torch at 1e-5 (the bound of test_groupnorm_layernorm_add_pe): several row blocks with a ragged
+    last one, both apply kernels on both sides of the 2^20 threshold, `up` maps that are and are not exactly half the size, with and
+    without ReLU, and a group whose mean is 1e3 x its standard deviation (group 1: the double-precision statistics keep its variance)"""
+    from s2d_amd import ops
+    g = torch.Generator(device="cuda").manual_seed(N * 1000003 + H * 1009 + W * 31 + C)
+    G = 32 if C >= 128 else 8                 # groups hold a multiple of 4 channels
+    x = torch.randn((N, H, W, C), device="cuda", generator=g) * 3 + 1
+    cg = C // G
+    x[..., cg:2 * cg] = torch.randn((N, H, W, cg), device="cuda", generator=g) + 1000.0
+    ga = torch.randn((C,), device="cuda", generator=g) * 0.1 + 1
+    be = torch.randn((C,), device="cuda", generator=g) * 0.1
+    def check(y, ref, tag, up_err=0.0):
+        # 1e-5 of the output scale on the whole tensor, and 1e-5 of ITS OWN scale on the offset group alone (the kernel keeps the statistics
+        # in double; measured on that group: at most 6.8e-6, which is the float32 rounding of a mean of 1e3 against a deviation of 1).
+        # With `up`: the source position of a tap is formed in float32 (by the kernel as by torch), a few units of 2^-24 of a coordinate
+        # that reaches 1 025 in the 2 x 2051 case, times the difference of neighbouring taps -- there the rule of
+        # tests/test_gpu_forward_c4.py holds for that term alone: max(1e-5, 2 x the error of torch's float32 interpolation of `up` against its
+        # float64 one, up_err, as a share of the output scale); the normalisation gets no allowance from float32 torch
+        r, r1 = _rel64(y, ref), _rel64(y[..., cg:2 * cg], ref[..., cg:2 * cg])
+        top, top1 = float(ref.abs().max()), float(ref[..., cg:2 * cg].abs().max())
+        print(f"groupnorm {N}x{H}x{W}x{C} {tag}: rel {r:.3e}, offset group alone {r1:.3e}, float32 interpolation error {up_err:.3e}")
+        assert r < max(1e-5, 2.0 * up_err / top) and r1 < max(1e-5, 2.0 * up_err / top1)
+
+    y = ops.groupnorm_nhwc(x, G, ga, be)
+    assert torch.equal(y, ops.groupnorm_nhwc(x, G, ga, be))
+    check(y, _groupnorm64(x, G, ga, be), "plain")
+    if up_hw is not None:
+        up = torch.randn((N, up_hw[0], up_hw[1], C), device="cuda", generator=g)
+        interp = lambda t: torch.nn.functional.interpolate(t.permute(0, 3, 1, 2), size=(H, W), mode="bilinear", align_corners=False)
+        up_err = float((interp(up).double() - interp(up.double())).abs().max())
+        for relu in (False, True):
+            y2 = ops.groupnorm_nhwc(x, G, ga, be, up=up, relu=relu)
+            check(y2, _groupnorm64(x, G, ga, be, up, relu), "up relu" if relu else "up", up_err)
+            if relu:
+                assert float(y2.min()) >= 0.0
+
+
+@pytest.mark.parametrize("rows", [4095, 4096, 4097, 4098, 4099, 4111])
+@pytest.mark.parametrize("with_res", [False, True])
+def test_layernorm_both_kernels_and_every_tail(rows, with_res):
+    """C = 256: layernorm_kernel below 4096 rows, layernorm256_kernel<4> from there (16 rows per workgroup, a wave's last rows recomputed
+    and not stored when rows % 4 != 0): against float64 at 1e-5 (test_groupnorm_layernorm_add_pe's bound), nothing written behind the
+    last row, and -- the promise beside layernorm256_kernel -- the same bits as layernorm_kernel on the same rows"""
+    from s2d_amd import ops
+    g = torch.Generator(device="cuda").manual_seed(rows * 2 + with_res)
+    C = 256
+    x = torch.randn((rows, C), device="cuda", generator=g) * 2 + 0.5
+    r = torch.randn((rows, C), device="cuda", generator=g) if with_res else None
+    ga = torch.randn((C,), device="cuda", generator=g) * 0.1 + 1
+    be = torch.randn((C,), device="cuda", generator=g) * 0.1
+    y = ops.layernorm(x, ga, be, res=r)
+    inp = x.double() if r is None else x.double() + r.double()
+    ref = torch.nn.functional.layer_norm(inp, (C,), ga.double(), be.double(), 1e-5)
+    assert _rel64(y, ref) < 1e-5
+    assert torch.equal(y, ops.layernorm(x, ga, be, res=r))
+    # the same rows in pieces of at most 4095 rows go through layernorm_kernel
+    parts = [ops.layernorm(x[s:s + 4095].contiguous(), ga, be, res=None if r is None else r[s:s + 4095].contiguous()) for s in range(0, rows, 4095)]
+    assert torch.equal(torch.cat(parts), y)
+    # into a larger buffer: the rows behind the last one keep their bits
+    from s2d_amd._lib import lib
+    wide = torch.full((rows + 16, C), 7.0, device="cuda")
+    lib().call("s2d_layernorm_f32", x, r, ga, be, rows, C, 1e-5, wide, ops._stream())
+    assert torch.equal(wide[:rows], y) and bool((wide[rows:] == 7.0).all())
+
+
+@pytest.mark.parametrize("N,H,W,C", [(2, 17, 23, 64), (1, 1, 5, 8), (3, 32, 31, 64), (1, 33, 2, 12)])
+def test_maxpool_odd_sizes_ties_and_argmax(N, H, W, C):
+    """3 x 3 / stride 2 / pad 1 max pool at odd and even extents with many exact ties in a window (values drawn from 5 levels): values
+    bit-equal to float64 max_pool2d of the same floats; want_idx returns the same values and a tap (ky * 3 + kx) that lies inside the map
+    and holds the maximum"""
+    from s2d_amd import ops
+    g = torch.Generator(device="cuda").manual_seed(H * 100 + W)
+    x = torch.randint(0, 5, (N, H, W, C), device="cuda", generator=g).float() - 2.0
+    ref = torch.nn.functional.max_pool2d(x.double().permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1)
+    y = ops.maxpool3x3s2(x)
+    assert torch.equal(y.double(), ref)
+    y2, idx = ops.maxpool3x3s2(x, want_idx=True)
+    assert torch.equal(y2, y) and int(idx.max()) < 9
+    Ho, Wo = y.shape[1:3]
+    ky, kx = (idx // 3).long(), (idx % 3).long()
+    yy = torch.arange(Ho, device="cuda")[None, :, None, None] * 2 - 1 + ky
+    xx = torch.arange(Wo, device="cuda")[None, None, :, None] * 2 - 1 + kx
+    assert bool(((yy >= 0) & (yy < H) & (xx >= 0) & (xx < W)).all())
+    n = torch.arange(N, device="cuda")[:, None, None, None].expand_as(idx)
+    c = torch.arange(C, device="cuda")[None, None, None, :].expand_as(idx)
+    assert torch.equal(x[n, yy, xx, c], y)
