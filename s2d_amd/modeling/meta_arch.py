@@ -17,7 +17,7 @@ from .criterion import TargetSet, VideoHungarianMatcher, VideoSetCriterion
 from .pixel_decoder import MSDeformAttnPixelDecoder
 from .postprocess import inference_video
 from .video_decoder import VideoMultiScaleMaskedTransformerDecoder
-from .window_inference import check_window_config, run_windows, window_kwargs
+from .window_inference import check_clip_size, check_window_config, run_windows, window_kwargs
 
 try:  # plug into detectron2's registries when it is installed (the drop-in boundary)
     from detectron2.modeling import META_ARCH_REGISTRY, SEM_SEG_HEADS_REGISTRY  # type: ignore
@@ -637,6 +637,7 @@ def _inference(net, images, batched_inputs, num_predictions, use_nms, nms_thresh
         if owner is not None:
             owner.last_windows = nwin
     else:
+        check_clip_size(images.shape[0], images.shape[1], images.shape[2])
         out = net(images, False)
         cls, ml, dims = out.class_logits[-1][0], out.mask_logits[-1][0], (out.T, out.hm, out.wm)
         del out

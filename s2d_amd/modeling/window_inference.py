@@ -26,6 +26,22 @@ def check_window_config(enabled, size, overlap, num_queries=None):
                          f"{MAX_WINDOW_QUERIES} queries")
 
 
+GEMM_OPERAND_BYTES = 0xFFFFFF00   # s2d_gemm_nt_f32 / s2d_conv2d_nhwc_f32 address an operand with 32-bit buffer offsets (gemm_bf16.hip)
+CLIP_CHANNELS = 256               # channels of the 1/4-resolution pixel-decoder maps, the widest activation a clip's GEMMs read
+
+
+def check_clip_size(T, Hp, Wp):
+    """refuse, as ValueError, a clip whose 1/4-resolution activation [T * Hp/4 * Wp/4, 256] f32 -- an operand of the mask-feature
+    GEMMs and convolutions -- exceeds what the dense kernels address (4 GB - 256 B; T = 71 at 720p is the last that fits).  Called
+    before the network runs, so nothing is launched; without it the forward ends in a bare `s2d_gemm_nt_f32 failed with code -1`."""
+    rows = int(T) * (int(Hp) // 4) * (int(Wp) // 4)
+    if rows * CLIP_CHANNELS * 4 > GEMM_OPERAND_BYTES:
+        per = (int(Hp) // 4) * (int(Wp) // 4) * CLIP_CHANNELS * 4
+        raise ValueError(f"a clip of {T} frames at {Hp} x {Wp} has {rows * CLIP_CHANNELS * 4} bytes of 1/4-resolution activations; the dense "
+                         f"kernels take at most {GEMM_OPERAND_BYTES} ({GEMM_OPERAND_BYTES // per} frames at this size).  Run longer videos "
+                         f"with MODEL.MASK_FORMER.TEST.WINDOW_INFERENCE (WINDOW_SIZE frames per window)")
+
+
 def window_kwargs(mf):
     """the three MODEL.MASK_FORMER.TEST.WINDOW_* keys as constructor arguments, checked (absent keys: the switch is off)"""
     t = getattr(mf, "TEST", None)
@@ -147,6 +163,7 @@ def run_windows(net, images, window_size, window_overlap, record=None):
     plan = plan_windows(T, window_size, window_overlap)
 
     def run(start, end):
+        check_clip_size(end - start, images.shape[1], images.shape[2])
         out = net(images[start:end], False)
         return (out.class_logits[-1][0], out.mask_logits[-1][0]), (out.Q, out.hm, out.wm)
 

@@ -163,7 +163,7 @@ def _sig_s2d_transpose_f32(src, rows, cols, lds, dst, ldd, stream):
     return (rows, cols, lds, ldd)
 
 
-LIB_CALLS = ("s2d_normalize_pad_nhwc4_f32", "s2d_transpose_f32")
+LIB_CALLS = {"s2d_normalize_pad_nhwc4_f32": _sig_s2d_normalize_pad_nhwc4_f32, "s2d_transpose_f32": _sig_s2d_transpose_f32}
 ENTRY_POINTS = {n[5:]: f for n, f in list(globals().items()) if n.startswith("_sig_") and n[5:] not in LIB_CALLS}
 ALIASES = {"dropout": "dropout_apply"}                    # ops.dropout is ops.dropout_apply
 NO_ROWS = {"matcher_cost", "lsap", "point_loss"}           # tests/test_gpu_c4_oracle.py checks them in isolation at this size
@@ -183,8 +183,10 @@ NOT_KERNELS = {
     "msda_backward_dev": "backward of msda_forward_dev", "msda_dev_status": "status read-back of the *_dev ops",
     "point_loss_kept_rows": "read-back of point_loss's workspace", "point_loss_backward": "backward (tests/test_gpu_backward.py)",
     "class_loss_backward": "backward (tests/test_gpu_backward.py)",
-    "infer_select": "inference", "infer_masks": "inference", "pack_mask_bits": "inference / evaluation", "mask_pair_counts": "evaluation",
-    "window_pair_counts": "windowed inference", "window_scatter_columns": "windowed inference", "mask_frame_areas": "demo rendering",
+    "infer_select": "eval path: signature and float64 rows in tests/test_gpu_eval_720p.py", "infer_masks": "eval path: tests/test_gpu_eval_720p.py",
+    "pack_mask_bits": "eval path / evaluator: tests/test_gpu_eval_720p.py", "mask_pair_counts": "eval path: tests/test_gpu_eval_720p.py",
+    "window_pair_counts": "windowed inference: tests/test_gpu_eval_720p.py records it, tests/test_gpu_window_inference.py checks it at that size",
+    "window_scatter_columns": "windowed inference: tests/test_gpu_eval_720p.py", "mask_frame_areas": "demo rendering",
     "render_instances": "demo rendering",
 }
 
@@ -198,10 +200,14 @@ def unknown_public_functions(ops):
 
 
 @contextlib.contextmanager
-def recording(ops, log, backward=None):
+def recording(ops, log, backward=None, entry_points=None, lib_calls=None):
     """wrap every forward entry point of s2d_amd.ops (and lib().call for LIB_CALLS) with a recorder of its shape signature; a call made from
-    inside another recorded entry point belongs to the outer row, and so does everything inside an entry point of `backward`"""
+    inside another recorded entry point belongs to the outer row, and so does everything inside an entry point of `backward`.
+    entry_points / lib_calls: the caller's own {name: signature function} maps in place of ENTRY_POINTS / LIB_CALLS (tests/
+    test_gpu_eval_720p.py records the eval path with the maps of this module plus its own)"""
     from tests import test_gpu_backward_c4 as bc4
+    entry_points = ENTRY_POINTS if entry_points is None else entry_points
+    lib_calls = LIB_CALLS if lib_calls is None else lib_calls
     saved, depth = [], [0]
 
     def wrap(name, fn, sig):
@@ -219,7 +225,7 @@ def recording(ops, log, backward=None):
         saved.append((obj, attr, getattr(obj, attr)))
         setattr(obj, attr, new)
 
-    for name, sig in ENTRY_POINTS.items():
+    for name, sig in entry_points.items():
         patch(ops, name, wrap(name, getattr(ops, name), sig))
     for alias, name in ALIASES.items():
         patch(ops, alias, getattr(ops, name))
@@ -230,8 +236,8 @@ def recording(ops, log, backward=None):
     raw = L.call
 
     def call(name, *a):
-        if depth[0] == 0 and name in LIB_CALLS:
-            log.append((name,) + tuple(globals()["_sig_" + name](*a)))
+        if depth[0] == 0 and name in lib_calls:
+            log.append((name,) + tuple(lib_calls[name](*a)))
         return raw(name, *a)
     L.call = call                                            # instance attribute in front of the class's method
     try:
@@ -633,9 +639,21 @@ def _case_ffn_fused(rep, g, M, F, has_ln1, has_ln2, row0, want_xn, post, has_pre
         d2, d3 = (None, None) if row0 is None else ((_P, _SEED, 1, row0), (_P, _SEED, 2, row0))
         s1 = ops.layernorm(x1, *ln1)
         h = ops.gemm_nt(s1, W1, bias=b1, relu=True, dropout=d2)
-        y2 = ops.layernorm(ops.gemm_nt(h, W2, bias=b2, res=s1, dropout=d3), *ln2)
+        if M * F * 4 > 0xFFFFFF00:
+            # the hidden activation, which only this form materialises, is a GEMM operand beyond the 32-bit buffer offsets of
+            # s2d_gemm_nt_f32 (4 GB - 256 B; M > 1 048 575 rows at F = 1024: no c4 row): the C ABI must refuse it, before any launch
+            # (h itself was written by the first GEMM -- the C side of a GEMM is addressed with 64-bit pointers -- and is compared with
+            # nothing: it only serves as the operand whose size is refused)
+            try:
+                ops.gemm_nt(h, W2, bias=b2, res=s1, dropout=d3)
+                refused = False
+            except RuntimeError as e:
+                refused = "s2d_gemm_nt_f32 failed with code -1" in str(e)
+            _check(rep, f"fuse_ffn = False form: hidden operand of {M * F * 4} bytes refused with S2D_ERR_ARG", refused)
+        else:
+            y2 = ops.layernorm(ops.gemm_nt(h, W2, bias=b2, res=s1, dropout=d3), *ln2)
+            rep.cmp("y, fuse_ffn = False form", y2, r64[0], r32[0], 2e-5)
         del h
-        rep.cmp("y, fuse_ffn = False form", y2, r64[0], r32[0], 2e-5)
 
 
 def _case_msda_fused_forward(rep, g, N, C, shapes, vstride, ostride, owidth, M, P):
