@@ -750,6 +750,7 @@ int s2d_aug_warp_mask_bits(const uint32_t *bits, long words_per_plane, const int
  * planes of a clip in one launch.  plan_dev: n_planes records {uint64 address of a source plane (bool / u8 [H, W], device memory),
  * int32 dx, int32 dy} (16 bytes each); out [n_planes][H][W] u8: out[j][y][x] = src_j[y + dy][x + dx] != 0 inside the frame, else 0 --
  * the reference's `_translate` (:58-68) for the instances an id's last sighting fills in, dx = dy = 0 for the instances a frame keeps.
+ * A u8 source may hold any non-zero value for "set"; every output byte is 0 or 1, on the aligned 16-byte path as on the byte path.
  * Which planes, and the (dx, dy) draws in the reference's `random.randint` order, are the host's plan (s2d_amd/data/copy_paste.py). */
 int s2d_shift_planes_u8(const void *plan_dev, int n_planes, int H, int W, uint8_t *out, hipStream_t stream);
 

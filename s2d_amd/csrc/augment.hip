@@ -372,8 +372,11 @@ __global__ __launch_bounds__(256) void copy_paste_frame_kernel(const uint8_t *__
 // plan row j = {address of the source plane (bool / u8 [H, W]), dx, dy}: out[j][y][x] = src[y + dy][x + dx] inside the frame, else 0.
 // Kept instances are rows with dx = dy = 0 (the reference concatenates them in front of the synthesised ones), filled instances read
 // the plane of the frame the id was last seen in.  16 output bytes per thread; a shifted row is read with unaligned byte loads only on
-// the planes that are shifted (dx != 0).
+// the planes that are shifted (dx != 0).  Every path writes `src != 0`: a u8 source may hold any non-zero value, the output is 0 / 1.
 struct ShiftPlan { unsigned long long src; int dx, dy; };
+
+// four bytes -> four bytes of (byte != 0): bit 7 of (b & 0x7f) + 0x7f is set iff the low seven bits are non-zero (no carry leaves a byte)
+__device__ __forceinline__ unsigned nonzero_bytes(unsigned w) { return ((((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) >> 7) & 0x01010101u; }
 
 __global__ __launch_bounds__(256) void shift_planes_kernel(const ShiftPlan *__restrict__ plan, int H, int W, uint8_t *__restrict__ out)
 {
@@ -384,7 +387,9 @@ __global__ __launch_bounds__(256) void shift_planes_kernel(const ShiftPlan *__re
     for (long i0 = ((long)blockIdx.x * 256 + threadIdx.x) * 16; i0 < npix; i0 += (long)gridDim.x * 256 * 16) {
         const bool fast = pl.dx == 0 && pl.dy == 0 && i0 + 16 <= npix && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
         if (fast) {
-            *reinterpret_cast<uint4 *>(dst + i0) = *reinterpret_cast<const uint4 *>(src + i0);
+            uint4 v = *reinterpret_cast<const uint4 *>(src + i0);
+            v.x = nonzero_bytes(v.x); v.y = nonzero_bytes(v.y); v.z = nonzero_bytes(v.z); v.w = nonzero_bytes(v.w);
+            *reinterpret_cast<uint4 *>(dst + i0) = v;
             continue;
         }
         int y = (int)(i0 / W), x = (int)(i0 - (long)y * W);
