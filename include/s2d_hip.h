@@ -745,6 +745,20 @@ int s2d_aug_warp_frames_hwc_u8(const uint8_t *frames, int T, int H0, int W0, voi
  * call).  S == 0 is a no-op. */
 int s2d_aug_warp_mask_bits(const uint32_t *bits, long words_per_plane, const int *plane_of, int S, int T, int H0, int W0,
                            const void *aug_frames_dev, int H1, int W1, uint8_t *out, unsigned *area, hipStream_t stream);
+/* Polygon annotations -> bit planes in the same layout (s2d_amd/data/image_clip.py: COCO image annotations as pseudo-clips).
+ * verts f32 [V][2] = (x, y) in source-pixel coordinates, any values; poly_off int32 [NP+1] = vertex range of every polygon;
+ * plane_off int32 [P+1] = polygon range of every plane (both DEVICE; the *_host copies are what is validated: offsets that are
+ * negative, decreasing or past V / NP are S2D_ERR_ARG).  Plane p goes to row dst_plane[p] of bits [rows][ceil(H*W/32)]
+ * (DEVICE int32 [P], distinct rows; NULL: row p, and rows >= P), so that the polygon planes of a record land between its RLE
+ * planes; a row outside [0, rows) is not written.  Pixel (x, y) is set iff its centre (x + 0.5, y + 0.5) is inside at least one
+ * of the plane's polygons by the even-odd rule: edge (x0, y0)-(x1, y1) counts when (y0 <= cy) != (y1 <= cy) and
+ * cx < x0 + (cy - y0) * (x1 - x0) / (y1 - y0) (float32); a polygon closes last vertex -> first; fewer than 3 vertices set
+ * nothing; a plane without polygons is all zero.  Every word of the P rows is stored exactly once (tail bits zero): no zero fill,
+ * no atomics.  rows * ceil(H*W/32) must stay below 2^31.  The rule is this library's: pycocotools frPoly parity is unpinned at
+ * boundary pixels. */
+int s2d_polygons_to_bits(const float *verts, int V, const int *poly_off, const int *poly_off_host, int NP, const int *plane_off,
+                         const int *plane_off_host, int P, const int *dst_plane, int rows, int H, int W, uint32_t *bits,
+                         hipStream_t stream);
 
 /* Sparse-mask densification of the trainer (`propagate_sparse_masks`, mask2former_video/engine/train_loop.py:30-156): all output
  * planes of a clip in one launch.  plan_dev: n_planes records {uint64 address of a source plane (bool / u8 [H, W], device memory),

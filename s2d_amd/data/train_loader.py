@@ -224,6 +224,10 @@ class YTVISTrainLoader:
     batch (a resumed run); threads: JPEG decode threads (<= 16); prefetch: batches prepared ahead.  `wait_s` accumulates the time
     the consumer spent blocked on the loader."""
 
+    # the mapper's halves: a subclass maps another kind of record through the same sampler, prefetch thread and side stream
+    _plan, _read, _stage = staticmethod(plan_clip), staticmethod(_read_frames), staticmethod(_stage_frames)
+    _launch, _finish = staticmethod(_launch_clip), staticmethod(_finish_clip)
+
     def __init__(self, records, settings, batch, seed, rank=0, world=1, aspect_grouping=True, start_iter=0, device=None,
                  threads=8, prefetch=2):
         if not 1 <= int(threads) <= MAX_THREADS:
@@ -250,7 +254,7 @@ class YTVISTrainLoader:
         for k, b in enumerate(batch_plan(self.records, self.seed, self.batch, self.rank, self.world, self.aspect_grouping)):
             if k < self.start_iter:
                 continue
-            yield [plan_clip(self.records[i], *clip_generators(self.seed, pos), self.settings) for pos, i in b]
+            yield [self._plan(self.records[i], *clip_generators(self.seed, pos), self.settings) for pos, i in b]
 
     def _produce(self, q, stop):
         try:
@@ -260,14 +264,14 @@ class YTVISTrainLoader:
                 for plans in self.plans():
                     if stop.is_set():
                         return
-                    futs = [_read_frames(p, pool, self.settings.fmt) for p in plans]       # every frame of the batch at once
-                    bufs = [_stage_frames(p, f) for p, f in zip(plans, futs)]
+                    futs = [self._read(p, pool, self.settings.fmt) for p in plans]         # every frame of the batch at once
+                    bufs = [self._stage(p, f) for p, f in zip(plans, futs)]
                     with torch.cuda.stream(side):
-                        outs = [_launch_clip(p, b, self.device) for p, b in zip(plans, bufs)]
+                        outs = [self._launch(p, b, self.device) for p, b in zip(plans, bufs)]
                         ev = torch.cuda.Event()
                         ev.record(side)
                     ev.synchronize()                         # this thread only: the pixel counts decide gt_ids
-                    item = ([_finish_clip(p, *o) for p, o in zip(plans, outs)], [(o[0], o[1]) for o in outs], ev)
+                    item = ([self._finish(p, *o) for p, o in zip(plans, outs)], [(o[0], o[1]) for o in outs], ev)
                     while not stop.is_set():
                         try:
                             q.put(item, timeout=0.1)

@@ -1,12 +1,15 @@
 """Training driver: `train_net_video.py` + detectron2's DefaultTrainer without detectron2.
 
     python -m s2d_amd.train --config-file X.yaml --train-json ann.json --image-root DIR --output-dir OUT
-           [--weights W.pth] [--resume] [--eval-gt val.json --eval-image-root DIR] [--threads N] [KEY VALUE ...]
+           [--train-format auto|ytvis|coco_image] [--weights W.pth] [--resume] [--eval-gt val.json --eval-image-root DIR]
+           [--threads N] [KEY VALUE ...]
 
 One process per GPU (or `torch.distributed.run`, gloo or nccl).  The model comes from MODEL.META_ARCHITECTURE through the registry,
 its weights from --weights / MODEL.WEIGHTS (checkpoint.load_checkpoint: a plain checkpoint fans out to student and teacher).  The
 optimizer is optim.build_optimizer, the LR scheduler solver.build_lr_scheduler.  Each iteration (engine/train_loop.py:690-770):
-next batch of the training loader (data/train_loader.py), copy-paste with DATALOADER.COPY_PASTE (`copy_and_paste(deepcopy(
+next batch of the training loader (data/train_loader.py for YTVIS videos; data/image_clip.py for a COCO image annotation
+file, RLE or polygons, every image a pseudo-clip of SAMPLING_FRAME_NUM augmented copies: --train-format coco_image, which `auto`
+picks for a JSON with `images` and no `videos`), copy-paste with DATALOADER.COPY_PASTE (`copy_and_paste(deepcopy(
 data[::-1]), data)`, :703), engine.run_step with the EMA momentum of the iteration, scheduler.step().
 
 EMA: a model with a teacher gets MODEL.MASK_FORMER.EMA_MOMENTUM at iteration 0; with EMA_MOMENTUM_SCHEDULE iteration i > 0 uses
@@ -47,7 +50,10 @@ LOG_PERIOD = 20
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="train a meta-architecture on a YTVIS-format annotation file")
     ap.add_argument("--config-file", required=True)
-    ap.add_argument("--train-json", required=True, help="YTVIS annotation JSON to train on (ground truth or pseudo labels)")
+    ap.add_argument("--train-json", required=True, help="YTVIS annotation JSON to train on (ground truth or pseudo labels), or a "
+                    "COCO image annotation JSON (--train-format)")
+    ap.add_argument("--train-format", choices=("auto", "ytvis", "coco_image"), default="auto",
+                    help="auto: coco_image when the JSON has `images` and no `videos`, else ytvis")
     ap.add_argument("--image-root", required=True, help="directory the JSON's file_names are relative to")
     ap.add_argument("--output-dir", required=True)
     ap.add_argument("--weights", default=None, help="initial weights, torch .pth or detectron2 .pkl (default: MODEL.WEIGHTS)")
@@ -176,6 +182,7 @@ def main(argv=None):
     import torch.distributed as dist
     from .checkpoint import load_checkpoint
     from .data.copy_paste import copy_and_paste
+    from .data.image_clip import COCOImageTrainLoader, detect_train_format, load_coco_image_train
     from .data.train_loader import YTVISTrainLoader, load_ytvis_train
     from .engine import run_step
     from .evaluate import evaluate_model
@@ -224,9 +231,16 @@ def main(argv=None):
     if rank == 0:
         print(json.dumps({"start_iter": start_iter, "max_iter": max_iter, "optimizer_step": optimizer._step, "seed": seed}), flush=True)
 
-    records = load_ytvis_train(a.train_json, a.image_root, dl.FILTER_EMPTY_ANNOTATIONS)
-    loader = YTVISTrainLoader.from_config(cfg, records, rank, world, seed, start_iter=start_iter, device=device, threads=a.threads,
-                                          prefetch=a.prefetch)
+    with open(a.train_json) as fh:
+        doc = json.load(fh)
+    fmt = detect_train_format(doc) if a.train_format == "auto" else a.train_format
+    if fmt == "coco_image":
+        records, loader_cls = load_coco_image_train(doc, a.image_root, dl.FILTER_EMPTY_ANNOTATIONS), COCOImageTrainLoader
+    else:
+        records, loader_cls = load_ytvis_train(doc, a.image_root, dl.FILTER_EMPTY_ANNOTATIONS), YTVISTrainLoader
+    del doc
+    loader = loader_cls.from_config(cfg, records, rank, world, seed, start_iter=start_iter, device=device, threads=a.threads,
+                                    prefetch=a.prefetch)
 
     def run_eval():
         if a.eval_gt:
