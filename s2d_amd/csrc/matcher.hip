@@ -377,7 +377,10 @@ __device__ __forceinline__ void matcher_cost_f16_body(const CostParams &p)
             for (int o = 16; o > 0; o >>= 1) { cmin = min(cmin, __shfl_xor(cmin, o, 64)); cmax = max(cmax, __shfl_xor(cmax, o, 64)); }
             if (cmax < 0) { cmin = 0; cmax = 0; }            // all-tail batch
             const int span = (cmax - cmin + 3) & ~1;         // cells cmin .. cmax + 1, rounded up to whole row pairs of the DMA
-            const bool staged = span <= SPANMAX;
+            // span < wm: the two runs are then disjoint pixel ranges.  On a map no wider than the run (wm <= SPANMAX) a lower tap row can
+            // start on the last pixel of the upper run, with its right tap the first pixel of the lower run -- not the next LDS row
+            // (a slack row lies between the runs) -- so such a batch takes the direct-gather path
+            const bool staged = span <= SPANMAX && span < p.wm;
             if (setq) {
                 const int ii[4] = {a.i00, a.i01, a.i10, a.i11};
                 const float ww[4] = {a.w00, a.w01, a.w10, a.w11};

@@ -36,6 +36,8 @@ def _cost64(oracle, logits, masks, tgt, coords, wc, wm, wd):
     sg = 1.0 / (1.0 + np.exp(-om))
     cost_dice = 1 - (2 * (sg @ tm.T) + 1) / (sg.sum(-1)[:, None] + tm.sum(-1)[None, :] + 1)
     l = logits.astype(np.float32)
+    if l.shape[-1] > 2:                                   # class-aware heads: -softmax(l)[:, 0] over all C1 columns, in float64
+        l = l.astype(np.float64)
     e = np.exp(l - l.max(-1, keepdims=True))
     cost_class = -np.repeat((e / e.sum(-1, keepdims=True))[:, :1].astype(np.float64), N, axis=1)
     # second value: the magnitude of the cost's terms (the sum itself can cancel to ~0: a random-init layer whose class, mask and

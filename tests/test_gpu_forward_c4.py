@@ -802,28 +802,41 @@ def _case_attn_mask_tap_index(rep, g, T, hm, wm, hl, wl):
 
 
 def _case_kd_targets(rep, g, B, C1, Q, T, hm, wm, ldq, H, W, Nmax, topk, want_labels):
-    """exact outside the excluded band (test_full_criterion_and_kd_targets_golden asserts array equality of the planes): the queries kept
-    are those of the top `topk` whose softmax score of class 0 reaches thr (scores drawn well away from thr: a float32 softmax decides
-    like float64), count and kept exact, every plane == (float64 bilinear interpolation > 0), nonempty == any() of the plane"""
+    """exact outside the excluded band (test_full_criterion_and_kd_targets_golden asserts array equality of the planes): the targets
+    kept are those of the top `topk` flat scores that reach thr (scores drawn well away from thr: a float32 softmax decides like float64,
+    and fewer than topk reach it, so thr alone decides), count and kept exact, every plane == (float64 bilinear interpolation > 0),
+    nonempty == any() of the plane.  C1 = 2: the score of class 0.  C1 > 2 (tests/test_gpu_classes_c4.py): a hot query q scores on
+    class q % C, the other foreground logits sit at -20; kept / label are the flat indices q*C + c that reach thr, in ascending order"""
     from s2d_amd import ops
-    assert C1 == 2 and topk >= Q
+    C = C1 - 1
+    assert C1 >= 2 and topk >= Q
     thr = 0.75
-    cls = torch.zeros((B, Q, 2), device=DEV)
+    cls = torch.zeros((B, Q, C1), device=DEV)
+    if C1 > 2:
+        cls[..., :C] = -20.0
     cls[..., 0] = -1.0 - torch.rand((B, Q), device=DEV, generator=g)                 # score <= 0.27
     for b in range(B):
         hot = torch.randperm(Q, device=DEV, generator=g)[:12 + b]
-        cls[b, hot, 0] = 3.0 + torch.rand((12 + b,), device=DEV, generator=g)        # score >= 0.95
+        heat = 3.0 + torch.rand((12 + b,), device=DEV, generator=g)                  # score >= 0.95
+        if C1 > 2:
+            cls[b, hot, 0] = -20.0
+        cls[b, hot, hot % C] = heat
     ml = _smooth_logits(g, B * Q * T, hm, wm).view(B, Q, T, hm, wm)
     pm = torch.zeros((B, T * hm * wm, ldq), device=DEV)
     pm[..., :Q] = ml.permute(0, 2, 3, 4, 1).reshape(B, T * hm * wm, Q)
     run = lambda: ops.kd_targets(cls, pm, (Q, T, hm, wm), H, W, Nmax, thr, topk, want_labels=want_labels)
     got, again = run(), run()
     tgt, count, kept, ne = got[:4]
-    score = torch.softmax(cls.double(), -1)[..., 0]
+    score = torch.softmax(cls.double(), -1)[..., :C].reshape(B, Q * C)
     for b in range(B):
         want = torch.nonzero(score[b] >= thr)[:, 0]
         n = int(count[b])
-        _check(rep, f"clip {b}: count {n} and kept queries", n == want.numel() and torch.equal(kept[b, :n].long().sort().values, want))
+        if C1 == 2:
+            _check(rep, f"clip {b}: count {n} and kept queries", n == want.numel() and torch.equal(kept[b, :n].long().sort().values, want))
+        else:
+            _check(rep, f"clip {b}: count {n}, kept queries and labels in ascending flat index", n == want.numel() and want_labels
+                   and torch.equal(kept[b, :n].long(), want // C) and torch.equal(got[4][b, :n].long(), want % C))
+            rep.same(f"clip {b}: labels second call", again[4][b, :n], got[4][b, :n])
         rep.same(f"clip {b}: planes second call", again[0][b, :n], tgt[b, :n])
         rep.same(f"clip {b}: nonempty second call", again[3][b, :n], ne[b, :n])
         if n != want.numel():
@@ -838,7 +851,7 @@ def _case_kd_targets(rep, g, B, C1, Q, T, hm, wm, ldq, H, W, Nmax, topk, want_la
         clean = ~excl.flatten(2).any(-1)
         _check(rep, f"clip {b}: nonempty on the {int(clean.sum())} of {n * T} planes without an excluded element",
                bool((((ne[b, :n] != 0) == ref.flatten(2).any(-1)) | ~clean).all()))
-    if want_labels:
+    if want_labels and C1 == 2:
         _check(rep, "no labels at two classes", got[4] is None)
 
 
