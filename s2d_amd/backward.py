@@ -7,12 +7,12 @@ dx is an NT GEMM against W^T.  dW contracts over the M rows (3e5..4e6): the cont
 in a fixed order, so the result is reproducible (shapes the TN kernel cannot take are transposed once and run as the batch
 of one NT-GEMM launch).  Same split-fp16 x3 arithmetic as the forward (fp32-class accuracy)."""
 import os
-import weakref
 
 import torch
 
 from . import ops
 from ._lib import lib
+from .weight_cache import DerivedCache, owner_of
 
 
 def _st():
@@ -278,97 +278,55 @@ def bias_grad(dy, out=None, beta=0.0):
     return out
 
 
-_WT = {}     # (data_ptr, shape) -> [W^T, version of the owning tensor, weak reference to the owning tensor]
-
-
-def _sweep(cache):
-    """drop the copies whose owning tensor is gone (called when a new key enters)"""
-    for k in [k for k, e in cache.items() if e[2]() is None]:
-        del cache[k]
+# The dgrad operands: cached per weight version (weight_cache.DerivedCache) and marked static, so that the dense kernels also cache their
+# pre-split images -- the dgrad GEMMs and convolutions then run on the same kernels as the forward's
+_WT = DerivedCache(static=True, floor=64)      # (data_ptr, shape, padded width) -> W^T
+_WF = DerivedCache(static=True, floor=64)      # (data_ptr, shape, strides) -> the flipped kernel
+_WS2 = DerivedCache(static=True, floor=64)     # (data_ptr, shape, strides) -> the 2 x 2 kernel of a stride-2 input gradient
+_WS2_IDX = {}
 
 
 def _transposed_weight(w, Np):
-    """W^T [K,Np] of a weight [N,K] (zero columns beyond N), cached per weight version and marked static so that the dense
-    kernels also cache its pre-split image: the dgrad GEMMs then run on the same kernels as the forward's"""
-    # the owner is identified BEFORE detaching: a detached alias is a fresh object on every call (and does not carry the library's
-    # version attribute), so keying on it would rebuild the copy at every call
-    base = w._base if w._base is not None else w
+    """W^T [K,Np] of a weight [N,K] (zero columns beyond N)"""
+    base = owner_of(w)
     w = w.detach()
-    key = (w.data_ptr(), tuple(w.shape), Np)
-    ent = _WT.get(key)
-    if ent is None or ent[2]() is not base:
-        wt = ops.mark_static(transpose(w.contiguous(), Np if Np != w.shape[0] else None))
-        wt._s2d_version = 0
-        _sweep(_WT)
-        ent = _WT[key] = [wt, ops.version_of(base), weakref.ref(base)]     # a WEAK reference: the copy must not keep a replaced weight alive
-    elif ent[1] != ops.version_of(base):
-        # the weight changed (an optimizer step): transpose into the SAME buffer and bump its version -- a fresh tensor per
-        # iteration would enter ops._SPLIT under a new address every time and never leave it (0.5 GB per iteration at c4)
+
+    def refresh(wt):            # the columns beyond N stay zero: only the first N are written
         wc = w.contiguous()
-        lib().call("s2d_transpose_f32", wc, wc.shape[0], wc.shape[1], wc.shape[1], ent[0], ent[0].shape[1], _st())
-        ent[0]._s2d_version += 1
-        ent[1] = ops.version_of(base)
-    return ent[0]
+        lib().call("s2d_transpose_f32", wc, wc.shape[0], wc.shape[1], wc.shape[1], wt, wt.shape[1], _st())
 
-
-_WF = {}
+    return _WT.get((w.data_ptr(), tuple(w.shape), Np), (base,), lambda: transpose(w.contiguous(), Np if Np != w.shape[0] else None), refresh)
 
 
 def _flipped_weight(w):
-    """the dgrad kernel of a convolution weight [Cout,KH,KW,Cin]: taps flipped, channels swapped -> [Cin,KH,KW,Cout]; cached per
-    weight version and marked static (like _transposed_weight), so that the dgrad convolutions run on the forward's kernels with
-    a pre-split image"""
-    base = w._base if w._base is not None else w          # (see _transposed_weight)
+    """the dgrad kernel of a convolution weight [Cout,KH,KW,Cin]: taps flipped, channels swapped -> [Cin,KH,KW,Cout]"""
+    base = owner_of(w)
     w = w.detach()
-    key = (w.data_ptr(), tuple(w.shape), tuple(w.stride()))
-    ent = _WF.get(key)
-    if ent is None or ent[2]() is not base:
-        wf = ops.mark_static(w.flip(1, 2).permute(3, 1, 2, 0).contiguous())
-        wf._s2d_version = 0
-        _sweep(_WF)
-        ent = _WF[key] = [wf, ops.version_of(base), weakref.ref(base)]
-    elif ent[1] != ops.version_of(base):                          # same buffer, new contents (see _transposed_weight)
-        ent[0].copy_(w.flip(1, 2).permute(3, 1, 2, 0))
-        ent[0]._s2d_version += 1
-        ent[1] = ops.version_of(base)
-    return ent[0]
+    return _WF.get((w.data_ptr(), tuple(w.shape), tuple(w.stride())), (base,), lambda: w.flip(1, 2).permute(3, 1, 2, 0).contiguous(),
+                   lambda wf: wf.copy_(w.flip(1, 2).permute(3, 1, 2, 0)))
 
 
-_WS2 = {}
-_WS2_IDX = {}
 _CONV_DGRAD_S2 = os.environ.get("S2D_CONV_DGRAD_S2", "1") != "0"       # 0: stride-2 3 x 3 input gradients through the zero-dilated form
 
 
 def _stride2_dgrad_weight(w):
     """the 2 x 2 kernel [4 Cin, 2, 2, Cout] of a stride-2 / pad-1 3 x 3 convolution's input gradient: output block (py, px) serves the input
     pixels (2a + py, 2b + px); along one axis an even pixel 2a meets tap 1 of output a, an odd pixel 2a + 1 tap 2 of output a and tap 0 of output
-    a + 1 -- with the convolution's pad 1 and the result read at (a + 1, b + 1), tap slot 0 sits on output a and slot 1 on output a + 1.
-    Cached per weight version and marked static (like _flipped_weight)."""
-    base = w._base if w._base is not None else w
+    a + 1 -- with the convolution's pad 1 and the result read at (a + 1, b + 1), tap slot 0 sits on output a and slot 1 on output a + 1."""
+    base = owner_of(w)
     w = w.detach()
-    key = (w.data_ptr(), tuple(w.shape), tuple(w.stride()))
-    ent = _WS2.get(key)
-    ver = ops.version_of(base)
-    if ent is not None and ent[2]() is base and ent[1] == ver:
-        return ent[0]
-    Co, _, _, Ci = w.shape
-    kmap = ((1, 9), (2, 0))                                             # [parity][slot] -> tap along one axis; 9 = no tap (a zero plane)
-    idx = _WS2_IDX.get(w.device)
-    if idx is None:
-        taps = [(kmap[py][jy], kmap[px][jx]) for py in range(2) for px in range(2) for jy in range(2) for jx in range(2)]
-        idx = _WS2_IDX[w.device] = torch.tensor([9 if 9 in t else t[0] * 3 + t[1] for t in taps], device=w.device, dtype=torch.long)
-    wp = torch.cat([w.permute(3, 1, 2, 0).reshape(Ci, 9, Co), torch.zeros((Ci, 1, Co), device=w.device, dtype=torch.float32)], 1)
-    w2 = wp.index_select(1, idx).view(Ci, 4, 2, 2, Co).permute(1, 0, 2, 3, 4).reshape(4 * Ci, 2, 2, Co).contiguous()
-    if ent is None or ent[2]() is not base:
-        w2 = ops.mark_static(w2)
-        w2._s2d_version = 0
-        _sweep(_WS2)
-        _WS2[key] = [w2, ver, weakref.ref(base)]
-        return w2
-    ent[0].copy_(w2)                                                    # same buffer, new contents (see _transposed_weight)
-    ent[0]._s2d_version += 1
-    ent[1] = ver
-    return ent[0]
+
+    def build():
+        Co, _, _, Ci = w.shape
+        kmap = ((1, 9), (2, 0))                                         # [parity][slot] -> tap along one axis; 9 = no tap (a zero plane)
+        idx = _WS2_IDX.get(w.device)
+        if idx is None:
+            taps = [(kmap[py][jy], kmap[px][jx]) for py in range(2) for px in range(2) for jy in range(2) for jx in range(2)]
+            idx = _WS2_IDX[w.device] = torch.tensor([9 if 9 in t else t[0] * 3 + t[1] for t in taps], device=w.device, dtype=torch.long)
+        wp = torch.cat([w.permute(3, 1, 2, 0).reshape(Ci, 9, Co), torch.zeros((Ci, 1, Co), device=w.device, dtype=torch.float32)], 1)
+        return wp.index_select(1, idx).view(Ci, 4, 2, 2, Co).permute(1, 0, 2, 3, 4).reshape(4 * Ci, 2, 2, Co).contiguous()
+
+    return _WS2.get((w.data_ptr(), tuple(w.shape), tuple(w.stride())), (base,), build, lambda w2: w2.copy_(build()))
 
 
 def input_grad(dy, w, res=None, gate=None, gate_scale=1.0, scale=None):

@@ -115,12 +115,12 @@ def read_state_dict(path):
 
 def invalidate_weight_caches(model):
     """drop every packed / pre-split weight image the library keeps for `model` (they are rebuilt at the next forward)"""
-    from . import ops
-    ops.clear_weight_cache()
+    from .weight_cache import PackedSlot, clear_weight_cache
+    clear_weight_cache()
     for m in model.modules():
-        for attr in ("_packed", "_fold", "_ws", "_kv_cache"):
-            if getattr(m, attr, None) is not None:
-                setattr(m, attr, None)
+        for slot in vars(m).values():
+            if isinstance(slot, PackedSlot):
+                slot.reset()
 
 
 def load_checkpoint(model, path_or_state_dict):

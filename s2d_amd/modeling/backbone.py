@@ -12,6 +12,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..weight_cache import PackedSlot
 
 R50_STAGES = (("res2", 3, 64, 256, 1), ("res3", 4, 128, 512, 2), ("res4", 6, 256, 1024, 2), ("res5", 3, 512, 2048, 2))
 
@@ -39,33 +40,27 @@ class ConvBN(nn.Module):
         nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")
         self.norm = FrozenBatchNorm2d(cout)
         self.stride, self.pad, self.k = stride, pad, k
-        self._packed = None
+        self._packed, self._fold, self._ws = PackedSlot(), PackedSlot(), PackedSlot()
+
+    def _norm_sources(self):
+        return self.norm.weight, self.norm.running_var, self.norm.bias, self.norm.running_mean
+
+    def _pack(self):
+        w = self.weight.detach().permute(0, 2, 3, 1)                 # [O,kh,kw,C]
+        if w.shape[-1] % 4:
+            w = torch.nn.functional.pad(w, (0, 4 - w.shape[-1] % 4))  # stem: Cin 3 -> 4 (input is NHWC4)
+        return w.float()
 
     def packed(self):
-        v = ops.version_of
-        key = (v(self.weight), self.weight.device, v(self.norm.weight), v(self.norm.running_var), v(self.norm.bias), v(self.norm.running_mean))
-        if self._packed is None or self._packed[0] != key:
-            w = self.weight.detach().permute(0, 2, 3, 1)             # [O,kh,kw,C]
-            if w.shape[-1] % 4:
-                w = torch.nn.functional.pad(w, (0, 4 - w.shape[-1] % 4))  # stem: Cin 3 -> 4 (input is NHWC4)
-            nkey = key[1:]                                                # the frozen statistics do not change with the weight:
-            if getattr(self, "_fold", None) is None or self._fold[0] != nkey:   # fold them once, not after every optimizer step
-                scale, shift = self.norm.fold()
-                self._fold = (nkey, scale.float(), shift.float())
-            scale, shift = self._fold[1], self._fold[2]
-            # own storage (1x1 kernels: permute + contiguous is still a view of the parameter), refreshed in place after an optimizer step
-            self._packed = (key, ops.repack(None if self._packed is None else self._packed[1], w.float()), scale, shift)
-        return self._packed[1:]
+        # own storage (1x1 kernels: permute + contiguous is still a view of the parameter), refreshed in place after an optimizer step;
+        # the frozen statistics do not change with the weight: they are folded once, not after every optimizer step
+        return self._packed.get((self.weight,), self._pack) + self._fold.get(self._norm_sources(), lambda: tuple(t.float() for t in self.norm.fold()))
 
     def packed_scaled(self):
         """the packed weight with the folded BatchNorm scale multiplied into its output channels (diag(scale) . W): the dgrad operand
         when the arriving gradient is d(pre-activation sum), not yet multiplied by the scale"""
         w, scale, _ = self.packed()
-        key = self._packed[0]
-        ws = getattr(self, "_ws", None)
-        if ws is None or ws[0] != key:
-            self._ws = ws = (key, ops.repack(None if ws is None else ws[1], w * scale.view(-1, 1, 1, 1)))
-        return ws[1]
+        return self._ws.get((self.weight,) + self._norm_sources(), lambda: w * scale.view(-1, 1, 1, 1))[0]
 
     def forward(self, x, res=None, relu=True):
         w, scale, shift = self.packed()

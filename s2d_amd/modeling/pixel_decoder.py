@@ -15,6 +15,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..weight_cache import PackedSlot
 
 
 class MSDeformAttn(nn.Module):
@@ -29,7 +30,7 @@ class MSDeformAttn(nn.Module):
         self.value_proj = nn.Linear(d_model, d_model)
         self.output_proj = nn.Linear(d_model, d_model)
         self._reset_parameters()
-        self._packed = None
+        self._packed = PackedSlot()
 
     def _reset_parameters(self):  # ms_deform_attn.py:66-80
         nn.init.constant_(self.sampling_offsets.weight.data, 0.)
@@ -52,15 +53,13 @@ class MSDeformAttn(nn.Module):
         bias [0 | b_value]: the offsets/logits bias travels in the row-periodic pos term of forward_fused."""
         ps = (self.sampling_offsets.weight, self.sampling_offsets.bias, self.attention_weights.weight, self.attention_weights.bias,
               self.value_proj.weight, self.value_proj.bias)
-        key = tuple(ops.version_of(p) for p in ps) + (ps[0].device,)
-        if self._packed is None or self._packed[0] != key:
+
+        def build():
             w_oa = torch.cat([ps[0].detach(), ps[2].detach()], 0)
             b_oa = torch.cat([ps[1].detach(), ps[3].detach()], 0)
-            w_all = torch.cat([w_oa, ps[4].detach()], 0)
-            b_all = torch.cat([torch.zeros_like(b_oa), ps[5].detach()], 0)
-            prev = (None,) * 5 if self._packed is None else self._packed            # refreshed in place after an optimizer step (ops.repack)
-            self._packed = (key, ops.repack(prev[1], w_all), ops.repack(prev[2], b_all), ops.repack(prev[3], w_oa), ops.repack(prev[4], b_oa))
-        return self._packed[1:]
+            return (torch.cat([w_oa, ps[4].detach()], 0), torch.cat([torch.zeros_like(b_oa), ps[5].detach()], 0), w_oa, b_oa)
+
+        return self._packed.get(ps, build)                         # (w_all, b_all, w_oa, b_oa), refreshed in place after an optimizer step
 
     def projection(self, pos):
         """what the previous layer's fused FFN launch needs to apply this layer's merged projection to its output rows (ops.ffn_fused
@@ -241,14 +240,10 @@ class _ConvGN(nn.Module):
         self.weight = nn.Parameter(torch.empty(cout, cin, k, k))
         nn.init.kaiming_uniform_(self.weight, a=1)  # fvcore c2_xavier_fill
         self.norm = nn.GroupNorm(32, cout)
-        self._packed = None
+        self._packed = PackedSlot()
 
     def packed(self):
-        key = (ops.version_of(self.weight), self.weight.device)
-        if self._packed is None or self._packed[0] != key:
-            w = self.weight.detach().permute(0, 2, 3, 1)
-            self._packed = (key, ops.repack(None if self._packed is None else self._packed[1], w))
-        return self._packed[1]
+        return self._packed.get((self.weight,), lambda: self.weight.detach().permute(0, 2, 3, 1))[0]
 
 
 class MSDeformAttnPixelDecoder(nn.Module):

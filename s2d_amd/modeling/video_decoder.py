@@ -14,6 +14,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..weight_cache import PackedSlot
 from .._lib import lib
 
 
@@ -218,7 +219,7 @@ class VideoMultiScaleMaskedTransformerDecoder(nn.Module):
         self.mask_embed = MLP(hidden_dim, hidden_dim, mask_dim, 3)
         self._pos_cache = {}
         self._tap_cache = {}
-        self._kv_cache = None
+        self._kv_cache = PackedSlot()
 
     @classmethod
     def from_config(cls, cfg, in_channels, mask_classification=True):  # :344-372
@@ -243,23 +244,18 @@ class VideoMultiScaleMaskedTransformerDecoder(nn.Module):
         stacked to [n*C, C] so that the memory of a level is read once for all of them instead of once per layer"""
         C = self.hidden_dim
         mh = [l.multihead_attn for l in self.transformer_cross_attention_layers]
-        key = tuple(ops.version_of(m.in_proj_weight) for m in mh) + tuple(ops.version_of(m.in_proj_bias) for m in mh) + (mh[0].in_proj_weight.device,)
-        if self._kv_cache is None or self._kv_cache[0] != key:
-            packs = []
-            prevs = [None] * 3 if self._kv_cache is None else self._kv_cache[1]
+
+        def build():
+            flat = ()
             for lvl in range(3):
-                ms = [mh[i] for i in range(self.num_layers) if i % 3 == lvl]
-                if not ms:                         # fewer than three layers: nobody reads this level
-                    packs.append(None)
-                    continue
-                wk = torch.cat([m.in_proj_weight.detach()[C:2 * C] for m in ms], 0)
-                bk = torch.cat([m.in_proj_bias.detach()[C:2 * C] for m in ms], 0)
-                wv = torch.cat([m.in_proj_weight.detach()[2 * C:] for m in ms], 0)
-                bv = torch.cat([m.in_proj_bias.detach()[2 * C:] for m in ms], 0)
-                pv = prevs[lvl] if prevs[lvl] is not None else (None,) * 4                    # refreshed in place after an optimizer step
-                packs.append((ops.repack(pv[0], wk), ops.repack(pv[1], bk), ops.repack(pv[2], wv), ops.repack(pv[3], bv)))
-            self._kv_cache = (key, packs)
-        return self._kv_cache[1]
+                ms = mh[lvl::3]
+                flat += (None,) * 4 if not ms else (                 # fewer than three layers: nobody reads this level
+                    torch.cat([m.in_proj_weight.detach()[C:2 * C] for m in ms], 0), torch.cat([m.in_proj_bias.detach()[C:2 * C] for m in ms], 0),
+                    torch.cat([m.in_proj_weight.detach()[2 * C:] for m in ms], 0), torch.cat([m.in_proj_bias.detach()[2 * C:] for m in ms], 0))
+            return flat
+
+        flat = self._kv_cache.get([m.in_proj_weight for m in mh] + [m.in_proj_bias for m in mh], build)
+        return [None if flat[i] is None else flat[i:i + 4] for i in (0, 4, 8)]
 
     def _project_memory(self, multi_scale, B, T, posl, tape=None):
         """keys and values of every layer, per level [B, T*h*w, n*C] (layer i reads columns (i // 3)*C .. of level i % 3).

@@ -1,10 +1,9 @@
 """Torch-tensor front ends of the C ABI (include/s2d_hip.h).  Tensors are plumbing only: device memory,
 the current stream, and the caching allocator for outputs.  Every function launches hand-written HIP."""
-import weakref
-
 import torch
 
 from ._lib import lib
+from .weight_cache import DerivedCache, bump_version, clear_weight_cache, mark_static, owner_of, repack, version_of  # noqa: F401  (ops.version_of etc.)
 
 
 PROFILE = None   # bench.py sets this to a list: (start_event, end_event, algorithmic flops) per dense launch
@@ -65,81 +64,25 @@ def _chk(t, dtype=torch.float32):
 
 
 _MODE = "f16x3"
-_SPLIT = {}      # (data_ptr, shape, row stride) -> (split image, version of the owning tensor, the owning tensor)
-
-
-def version_of(t):
-    """content version of a tensor for this library's caches: torch's in-place counter of the owning tensor + the count of rewrites
-    torch cannot see (the multi-tensor optimizer kernel updates parameters and EMA copies through raw pointers: bump_version)"""
-    base = t._base if t._base is not None else t
-    return base._version + getattr(base, "_s2d_version", 0)
-
-
-def bump_version(t):
-    """declare that t's storage was rewritten behind torch's back (a kernel of this library wrote through its raw pointer)"""
-    base = t._base if t._base is not None else t
-    base._s2d_version = getattr(base, "_s2d_version", 0) + 1
-
-
-def repack(old, new):
-    """A module's cached packed weight copy after its sources changed: when the previous copy has the same shape it is overwritten
-    IN PLACE (torch's counter moves, so the caches hanging off its address -- split images, transposed / flipped copies -- refresh
-    into their existing buffers); otherwise `new` becomes the copy.  A fresh tensor per optimizer step would leave a dead generation of
-    every such cache behind per step."""
-    if old is not None and old.shape == new.shape and old.device == new.device and old.dtype == new.dtype:
-        old.copy_(new)
-        return old
-    new = new.contiguous()
-    if new._base is not None:
-        new = new.clone()
-    return mark_static(new)
-
-
-def mark_static(t):
-    """Declare a tensor a static weight (a packed / concatenated copy of parameters that its module caches): dense launches
-    reading it as the B operand may then use a cached pre-split fp16 image instead of splitting it in every launch."""
-    t._s2d_static = True
-    return t
-
-
-def clear_weight_cache():
-    _SPLIT.clear()
-    _FFN_PACK.clear()
-
-
-_SWEEP = [256]
-
-
-def _sweep_split_cache():
-    """drop the images whose owning tensor is gone (called when a new key enters; amortised)"""
-    if len(_SPLIT) < _SWEEP[0]:
-        return
-    for k in [k for k, e in _SPLIT.items() if e[2]() is None]:
-        del _SPLIT[k]
-    _SWEEP[0] = max(256, 2 * len(_SPLIT))
+_SPLIT = DerivedCache()      # (data_ptr, N, K, row stride, dense mode) -> the split image of the tensor that owns that address
 
 
 def _static_split(B, N, K, ldb):
     """cached fp16 hi/lo image of a static weight matrix, or None (dynamic tensor / other dense mode)"""
     if _MODE == "f32" or N * ((K + 31) // 32) * 128 > 0xFFFFFF00:
         return None
-    base = B._base if B._base is not None else B
+    base = owner_of(B)
     if not (isinstance(base, torch.nn.Parameter) or getattr(base, "_s2d_static", False) or getattr(B, "_s2d_static", False)):
         return None
-    key = (B.data_ptr(), N, K, ldb, _MODE)      # the image is fp16 hi / scaled lo or bf16 hi / lo, by the mode in force
-    ent = _SPLIT.get(key)
-    ver = base._version + getattr(base, "_s2d_version", 0)     # _s2d_version: buffers this library rewrites in place (backward.py)
-    if ent is None or ent[1] != ver or ent[2]() is not base:
-        # a stale image of the same tensor is overwritten in place (same size): steady-state training allocates nothing here
-        same = ent is not None and ent[2]() is base
-        img = ent[0] if same else torch.empty((lib().call("s2d_split_weights_words", N, K),), device=B.device, dtype=torch.int32)
+
+    def split(img):
         lib().call("s2d_split_weights_f16", B, N, K, ldb, img, _stream())
-        if not same:
-            _sweep_split_cache()
-        # a WEAK reference to the owner: a packed copy its module has replaced (every optimizer step re-packs) dies, and its image
-        # with it at the next sweep; an address recycled under the same key fails the identity test above and is split again
-        _SPLIT[key] = ent = (img, ver, weakref.ref(base))
-    return ent[0]
+        return img
+
+    # the image is fp16 hi / scaled lo or bf16 hi / lo, by the mode in force; a stale image of the same tensor is overwritten in place
+    # (same size): steady-state training allocates nothing here
+    return _SPLIT.get((B.data_ptr(), N, K, ldb, _MODE), (base,),
+                      lambda: split(torch.empty((lib().call("s2d_split_weights_words", N, K),), device=B.device, dtype=torch.int32)), split)
 
 
 def set_dense_mode(mode):
@@ -275,32 +218,23 @@ def gemm_nt_presplit(A_split, M, K, B, bias=None, res=None, relu=False, out=None
     return out
 
 
-_FFN_PACK = {}    # (W1 ptr, W2 ptr, Wpost ptr, F, Npost) -> (image, versions, weakrefs of the owners)
-
-
-def _owner(t):
-    return t._base if t._base is not None else t
+_FFN_PACK = DerivedCache(floor=64)    # (W1 ptr, W2 ptr, Wpost ptr, Wpre ptr, F, Npost, Wpre given) -> the image of the tensors that own those addresses
 
 
 def _ffn_pack(W1, W2, Wpost=None, Wpre=None):
-    """cached MFMA-fragment image of an FFN's two weight matrices (+ the projection applied behind it), s2d_ffn_pack_f16; rebuilt when
-    an owner changes (parameter version; packed copies are replaced by their module, which changes the key)"""
+    """cached MFMA-fragment image of an FFN's two weight matrices (+ the projection applied behind it), s2d_ffn_pack_f16; rewritten when
+    an owner changes (parameters and packed copies alike: their modules refresh those in place)"""
     F, C = W1.shape
     Np = 0 if Wpost is None else Wpost.shape[0]
     ts = (W1, W2) + (() if Wpost is None else (Wpost,)) + (() if Wpre is None else (Wpre,))
-    key = tuple(t.data_ptr() for t in ts) + (F, Np, Wpre is not None)
-    owners = [_owner(t) for t in ts]
-    ver = tuple(o._version + getattr(o, "_s2d_version", 0) for o in owners)
-    ent = _FFN_PACK.get(key)
-    if ent is None or ent[1] != ver or any(r() is not o for r, o in zip(ent[2], owners)):
-        same = ent is not None and all(r() is o for r, o in zip(ent[2], owners))
-        img = ent[0] if same else torch.empty((lib().call("s2d_ffn_pack_words", C, F, Np, int(Wpre is not None)),), device=W1.device, dtype=torch.int32)
+
+    def pack(img):
         lib().call("s2d_ffn_pack_f16", W1, W2, C, F, Wpost, Np, Wpre, img, _stream())
-        if not same and len(_FFN_PACK) >= 64:
-            for k in [k for k, e in _FFN_PACK.items() if any(r() is None for r in e[2])]:
-                del _FFN_PACK[k]
-        _FFN_PACK[key] = ent = (img, ver, [weakref.ref(o) for o in owners])
-    return ent[0]
+        return img
+
+    return _FFN_PACK.get(tuple(t.data_ptr() for t in ts) + (F, Np, Wpre is not None), tuple(owner_of(t) for t in ts),
+                         lambda: pack(torch.empty((lib().call("s2d_ffn_pack_words", C, F, Np, int(Wpre is not None)),), device=W1.device,
+                                                  dtype=torch.int32)), pack)
 
 
 def ffn_fusable(W1, W2):

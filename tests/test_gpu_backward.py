@@ -61,17 +61,20 @@ def test_bias_gradient_inside_the_weight_gradient_kernel(M, N, K):
 def test_weight_caches_follow_the_multi_tensor_optimizer_step():
     """FullModelGradientClippingAdamW.step() rewrites the parameters (and the EMA copies) through raw pointers, which torch's version
     counters do not see: the library's version (ops.version_of) must move, so that the pre-split / packed / transposed weight copies
-    are rebuilt -- a dense launch, a ConvBN, the one-launch FFN and a dgrad after a step against torch on the updated parameters"""
+    are rebuilt -- a dense launch, a ConvBN, the one-launch FFN, a linear dgrad and a stride-2 convolution dgrad after a step against
+    torch on the updated parameters"""
     from s2d_amd import backward as B, ops
     from s2d_amd.modeling.backbone import ConvBN
     from s2d_amd.optim import FullModelGradientClippingAdamW
     torch.manual_seed(0)
     lin, lin2, conv = torch.nn.Linear(256, 1024).to(DEV), torch.nn.Linear(1024, 256).to(DEV), ConvBN(64, 64, 3, 1, 1).to(DEV)
-    ema = [p.detach().clone() for p in list(lin.parameters()) + list(lin2.parameters()) + [conv.weight]]
-    params = list(lin.parameters()) + list(lin2.parameters()) + [conv.weight]
+    conv2 = ConvBN(64, 64, 3, 2, 1).to(DEV)
+    params = list(lin.parameters()) + list(lin2.parameters()) + [conv.weight, conv2.weight]
+    ema = [p.detach().clone() for p in params]
     opt = FullModelGradientClippingAdamW([{"params": params, "lr": 0.05, "weight_decay": 0.0}], lr=0.05, clip_norm=0.0, ema_params=ema)
     x = torch.randn(300, 256, device=DEV)
     img = torch.randn(2, 12, 16, 64, device=DEV)
+    dy2 = torch.randn(2, 6, 8, 64, device=DEV)                       # a gradient of conv2's output
     g1, be1, g2, be2 = (torch.ones(256, device=DEV), torch.zeros(256, device=DEV), torch.ones(256, device=DEV), torch.zeros(256, device=DEV))
 
     def device_side():
@@ -80,7 +83,8 @@ def test_weight_caches_follow_the_multi_tensor_optimizer_step():
         f = ops.ffn_fused(x, lin.weight, lin.bias, lin2.weight, lin2.bias, ln1=(g1, be1), ln2=(g2, be2))
         d = B.input_grad(y, lin.weight)
         e = ops.gemm_nt(x, ema[0], bias=ema[1])
-        return y, c, f, d, e
+        g = B.conv_input_grad(dy2, conv2.packed()[0], 2, 1, (12, 16))
+        return y, c, f, d, e, g
 
     def torch_side():
         F = torch.nn.functional
@@ -89,18 +93,23 @@ def test_weight_caches_follow_the_multi_tensor_optimizer_step():
         c = torch.relu(F.conv2d(img.permute(0, 3, 1, 2), conv.weight, padding=1) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)).permute(0, 2, 3, 1)
         s1 = F.layer_norm(x, (256,))
         f = F.layer_norm(s1 + F.linear(torch.relu(F.linear(s1, lin.weight, lin.bias)), lin2.weight, lin2.bias), (256,))
-        return y, c, f, y @ lin.weight, F.linear(x, ema[0], ema[1])
+        g = torch.nn.grad.conv2d_input((2, 64, 12, 16), conv2.weight, dy2.permute(0, 3, 1, 2), stride=2, padding=1).permute(0, 2, 3, 1)
+        return y, c, f, y @ lin.weight, F.linear(x, ema[0], ema[1]), g
 
     sizes = []
     for it in range(6):
         for a, b in zip(device_side(), torch_side()):
             assert float((a - b.detach()).abs().max()) < 2e-4 * float(b.abs().max()) + 1e-5, it
+        # the buffers the launches above read (asked for before the step, so that these lookups are hits and refresh nothing themselves)
+        wt, ws2 = B._transposed_weight(lin.weight, 1024), B._stride2_dgrad_weight(conv2.packed()[0])
+        ptrs = (wt.data_ptr(), ws2.data_ptr(), ops._static_split(wt, 256, 1024, 1024).data_ptr(), ops._static_split(lin.weight, 1024, 256, 256).data_ptr())
         for p in params:
             p.grad.copy_(torch.randn_like(p))
         opt.step(ema_momentum=0.9)
-        sizes.append((len(ops._SPLIT), len(ops._FFN_PACK), len(B._WT), len(B._WF), id(conv.packed()[0])))
-    # ... and the refresh happens IN PLACE: no cache gains an entry per step, the packed ConvBN weight keeps its buffer (a copy that
-    # kept a replaced weight alive, or a fresh packed tensor per step, leaks a generation of every cache per iteration)
+        sizes.append((len(ops._SPLIT), len(ops._FFN_PACK), len(B._WT), len(B._WF), len(B._WS2), id(conv.packed()[0])) + ptrs)
+    # ... and the refresh happens IN PLACE: no cache gains an entry per step, the packed ConvBN weight, the transposed and the stride-2
+    # dgrad weights and two split images keep their buffers (a copy that kept a replaced weight alive, or a fresh packed tensor per step,
+    # leaks a generation of every cache per iteration)
     assert sizes[2] == sizes[5], sizes
 
 
