@@ -16,7 +16,7 @@
 // a lane owns one query column: the online-softmax max/sum are per-lane scalars, and the probabilities P
 // (the accumulator registers) are directly the B operand of O^T[d][q] += V^T . P^T -- no LDS round trip
 // for P and no cross-lane rescale.  Partial (O, m, l) per key split are merged by a second tiny kernel.
-#include "common.h"
+#include "split_f16.h"
 #include <stdlib.h>
 
 namespace {
@@ -108,7 +108,6 @@ __global__ __launch_bounds__(256) void attn_mask_kernel(const float *__restrict_
     }
 }
 
-
 // ---- regression variant ------------------------------------------------------------------------
 // Round 1's form of the kernel above (guarded 4-B tap loads, the four taps of a query consumed together).  Under the
 // compiler's SLP vectorisation its arithmetic became v_pk_mul_f32 issued straight behind `s_waitcnt vmcnt(0)`, with the
@@ -167,21 +166,7 @@ __global__ __launch_bounds__(256) void attn_mask_kernel_dword_taps(const float *
 }
 
 // ------------------------------------------------------------------------------------------------
-// split-fp16 helpers (the scheme of gemm_bf16.hip: x = h + l * 2^-11, h = fp16_rtz(x), l = fp16_rtz((x - h) * 2^11))
-typedef __fp16 h16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void split4_h(const f32x4 v, u32x2 &hi, u32x2 &lo)
-{
-    const h16x2 ha = __builtin_amdgcn_cvt_pkrtz(v[0], v[1]), hb = __builtin_amdgcn_cvt_pkrtz(v[2], v[3]);
-    const f32x2 a = {v[0], v[1]}, b = {v[2], v[3]};
-    const f32x2 ra = (a - __builtin_convertvector(ha, f32x2)) * 2048.f, rb = (b - __builtin_convertvector(hb, f32x2)) * 2048.f;
-    const h16x2 la = __builtin_amdgcn_cvt_pkrtz(ra[0], ra[1]), lb = __builtin_amdgcn_cvt_pkrtz(rb[0], rb[1]);
-    hi[0] = __builtin_bit_cast(unsigned int, ha); hi[1] = __builtin_bit_cast(unsigned int, hb);
-    lo[0] = __builtin_bit_cast(unsigned int, la); lo[1] = __builtin_bit_cast(unsigned int, lb);
-}
+// split-fp16 x3 attention: both products of the forward and all five of the backward on the scheme of split_f16.h
 
 struct AttnParams {
     const float *q, *k, *v;      // q [B][Q][C] (projected, unscaled); k, v [B][K][C]
@@ -219,8 +204,8 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(AttnParams p)
             f32x4 t1 = qok ? *reinterpret_cast<const f32x4 *>(qp + 16 * st + 4) : f32x4(0.f);
             t0 *= p.qscale; t1 *= p.qscale;
             u32x2 h0, l0, h1, l1;
-            split4_h(t0, h0, l0);
-            split4_h(t1, h1, l1);
+            split4(t0, h0, l0);
+            split4(t1, h1, l1);
             const u32x4 hv = {h0[0], h0[1], h1[0], h1[1]}, lv = {l0[0], l0[1], l1[0], l1[1]};
             qh[st] = __builtin_bit_cast(f16x8, hv);
             ql[st] = __builtin_bit_cast(f16x8, lv);
@@ -257,11 +242,11 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(AttnParams p)
     };
     auto store_tile = [&](int buf) {
         u32x2 kh, kl;
-        split4_h(rk, kh, kl);
+        split4(rk, kh, kl);
         *reinterpret_cast<u32x2 *>(&Ks[buf][srow][sc4 * 2]) = kh;
         *reinterpret_cast<u32x2 *>(&Ks[buf][srow][16 + sc4 * 2]) = kl;
         u32x2 vh, vl;
-        split4_h(rv, vh, vl);
+        split4(rv, vh, vl);
         const int k16 = srow & 15;
         const int pos = (srow >> 4) * 16 + ((k16 >> 2) & 1) * 8 + (((k16 >> 3) << 2) | (k16 & 3));
 #pragma unroll
@@ -299,13 +284,13 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(AttnParams p)
             s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[st], s, 0, 0, 0);
         }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] += sx[r] * (1.0f / 2048.0f);
+        for (int r = 0; r < 16; ++r) s[r] = join(s[r], sx[r]);
         // mask + tail, tile max  (only the last tile of the key range can have a tail: uniform branch)
         float tmax = -INFINITY;
         const int kleft = p.K - tile * KT;                   // keys of this tile that exist (>= KT except on the last tile)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int kr = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int kr = (r & 3) + 8 * (r >> 2) + 4 * h;      // mfma32_row (common.h) written out
             bool dead = kr >= kleft;
             if (use_mask) dead = dead || ((Ms[cur][kr][wv] >> l32) & 1u);
             s[r] = dead ? -INFINITY : s[r];
@@ -332,9 +317,10 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(AttnParams p)
             u32x4 phv, plv;
 #pragma unroll
             for (int jp = 0; jp < 4; ++jp) {
+                // split2 (split_f16.h) written out, as in frag_from_acc below
                 const float a = s[8 * st + 2 * jp], bq = s[8 * st + 2 * jp + 1];
                 const h16x2 hh = __builtin_amdgcn_cvt_pkrtz(a, bq);
-                const h16x2 ll = __builtin_amdgcn_cvt_pkrtz((a - (float)hh[0]) * 2048.f, (bq - (float)hh[1]) * 2048.f);
+                const h16x2 ll = __builtin_amdgcn_cvt_pkrtz((a - (float)hh[0]) * SPLIT_SCALE, (bq - (float)hh[1]) * SPLIT_SCALE);
                 phv[jp] = __builtin_bit_cast(unsigned int, hh);
                 plv[jp] = __builtin_bit_cast(unsigned int, ll);
             }
@@ -356,8 +342,8 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(AttnParams p)
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int d = (r & 3) + 8 * (r >> 2) + 4 * h;
-        p.wo[(pidx * 32 + d) * 128 + q] = o[r] + ox[r] * (1.0f / 2048.0f);
+        const int d = (r & 3) + 8 * (r >> 2) + 4 * h;            // mfma32_row (common.h) written out
+        p.wo[(pidx * 32 + d) * 128 + q] = join(o[r], ox[r]);
     }
 }
 
@@ -461,7 +447,6 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnBwdParams p)
     for (int w = 0; w < QW; ++w) mw[w] &= ~ign[w];     // bit set = this (query, key) pair does not attend
     // two channels per vector instruction (v_pk_fma_f32): the loop is bound by its 128 multiply-adds per (query, key) pair.  Even /
     // odd channels accumulate separately and are added at the end: a fixed order.
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     for (int qq = quarter; qq < p.Q; qq += 4) {
         if ((mw[qq >> 5] >> (qq & 31)) & 1u) continue;
         f32x2 s2v = {0.f, 0.f}, dpv = {0.f, 0.f};
@@ -561,7 +546,6 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(AttnBwdParams p)
             const uint32_t w = ms[r][qq >> 5];
             const bool beyond = (long)t * BT + r >= p.K;
             if (beyond || (use_mask && ((w >> (qq & 31)) & 1u))) continue;
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
             f32x2 s2v = {0.f, 0.f}, dpv = {0.f, 0.f};
 #pragma unroll
             for (int d = 0; d < 32; d += 2) {
@@ -622,7 +606,8 @@ constexpr int KROW = 40;          // halves per row of a wave's transposed K til
 
 __device__ __forceinline__ int perm16(int k16) { return ((k16 >> 2) & 1) * 8 + (((k16 >> 3) << 2) | (k16 & 3)); }
 
-// 8 accumulator registers (one MFMA k-step's worth of a C-layout tile) -> hi / lo B fragments
+// 8 accumulator registers (one MFMA k-step's worth of a C-layout tile) -> hi / lo B fragments.  The split is written out (split2 of
+// split_f16.h, with the high part converted per element): the form these two kernels were compiled with
 __device__ __forceinline__ void frag_from_acc(const float *v, f16x8 &fh, f16x8 &fl)
 {
     u32x4 hv, lv;
@@ -630,7 +615,7 @@ __device__ __forceinline__ void frag_from_acc(const float *v, f16x8 &fh, f16x8 &
     for (int jp = 0; jp < 4; ++jp) {
         const float a = v[2 * jp], bq = v[2 * jp + 1];
         const h16x2 hh = __builtin_amdgcn_cvt_pkrtz(a, bq);
-        const h16x2 ll = __builtin_amdgcn_cvt_pkrtz((a - (float)hh[0]) * 2048.f, (bq - (float)hh[1]) * 2048.f);
+        const h16x2 ll = __builtin_amdgcn_cvt_pkrtz((a - (float)hh[0]) * SPLIT_SCALE, (bq - (float)hh[1]) * SPLIT_SCALE);
         hv[jp] = __builtin_bit_cast(unsigned int, hh);
         lv[jp] = __builtin_bit_cast(unsigned int, ll);
     }
@@ -664,8 +649,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             g = *reinterpret_cast<const f32x4 *>(p.dout + ((long)b * p.Q + qq) * p.C + hd * 32 + c4 * 4);
         }
         u32x2 ah, al, gh, gl;
-        split4_h(a, ah, al);
-        split4_h(g, gh, gl);
+        split4(a, ah, al);
+        split4(g, gh, gl);
         *reinterpret_cast<u32x2 *>(&L.Qs[qq][c4 * 2]) = ah; *reinterpret_cast<u32x2 *>(&L.Qs[qq][16 + c4 * 2]) = al;
         *reinterpret_cast<u32x2 *>(&L.Gs[qq][c4 * 2]) = gh; *reinterpret_cast<u32x2 *>(&L.Gs[qq][16 + c4 * 2]) = gl;
         const int pos = (qq & ~15) + perm16(qq & 15);
@@ -727,8 +712,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int i = 0; i < 4; ++i) {
             const int row = srow + 8 * i;
             u32x2 kh, kl, vh, vl;
-            split4_h(rk[i], kh, kl);
-            split4_h(rv[i], vh, vl);
+            split4(rk[i], kh, kl);
+            split4(rv[i], vh, vl);
             *reinterpret_cast<u32x2 *>(&L.Ks[wv][row][sc4 * 2]) = kh; *reinterpret_cast<u32x2 *>(&L.Ks[wv][row][16 + sc4 * 2]) = kl;
             *reinterpret_cast<u32x2 *>(&L.Vs[wv][row][sc4 * 2]) = vh; *reinterpret_cast<u32x2 *>(&L.Vs[wv][row][16 + sc4 * 2]) = vl;
             const int pos = (row & ~15) + perm16(row & 15);
@@ -797,10 +782,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
                     for (int jj = 0; jj < 8; ++jj) {
                         const int r = 8 * st + jj;
-                        const int kr = (r & 3) + 8 * (r >> 2) + 4 * h;
+                        const int kr = mfma32_row(r, h);
                         const bool dead = (L.Ms[wv][kr][j] >> l32) & 1u;
-                        const float arg = dead ? -INFINITY : (s[r] + sx[r] * (1.0f / 2048.0f)) - lq;       // exp2(-inf) = 0
-                        dst[jj] = __builtin_amdgcn_exp2f(arg) * ((dp[r] + dpx[r] * (1.0f / 2048.0f)) - dlq);
+                        const float arg = dead ? -INFINITY : join(s[r], sx[r]) - lq;       // exp2(-inf) = 0
+                        dst[jj] = __builtin_amdgcn_exp2f(arg) * (join(dp[r], dpx[r]) - dlq);
                     }
                     f16x8 bh, bl;
                     frag_from_acc(dst, bh, bl);
@@ -811,7 +796,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     dq[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ath, bh, dq[j], 0, 0, 0);
                 }
 #pragma unroll
-                for (int r = 0; r < 16; ++r) dq[j][r] = __builtin_fmaf(cx[r], 1.0f / 2048.0f, dq[j][r]);
+                for (int r = 0; r < 16; ++r) dq[j][r] = __builtin_fmaf(cx[r], SPLIT_INV, dq[j][r]);     // join_fma (split_f16.h) written out
             }
             // ---- lane = key: S[q][key], dP[q][key]
             __builtin_amdgcn_sched_barrier(0);
@@ -843,10 +828,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                         for (int e = 0; e < 4; ++e) {
                             const int r = 8 * st + 4 * g + e;
                             const bool dead = (mkey[j] >> (q0 - 32 * j + e)) & 1u;
-                            const float arg = dead ? -INFINITY : (s[r] + sx[r] * (1.0f / 2048.0f)) - l4[e];
+                            const float arg = dead ? -INFINITY : join(s[r], sx[r]) - l4[e];
                             const float pr = __builtin_amdgcn_exp2f(arg);
                             pv[4 * g + e] = pr;
-                            dsv[4 * g + e] = pr * ((dp[r] + dpx[r] * (1.0f / 2048.0f)) - d4[e]);
+                            dsv[4 * g + e] = pr * (join(dp[r], dpx[r]) - d4[e]);
                         }
                     }
                     f16x8 ph, pl, sh, sl;
@@ -863,7 +848,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     dk = __builtin_amdgcn_mfma_f32_32x32x16_f16(qth, sh, dk, 0, 0, 0);
                 }
 #pragma unroll
-                for (int r = 0; r < 16; ++r) { dk[r] = __builtin_fmaf(dkx[r], 1.0f / 2048.0f, dk[r]); dv[r] = __builtin_fmaf(dvx[r], 1.0f / 2048.0f, dv[r]); }
+                for (int r = 0; r < 16; ++r) { dk[r] = __builtin_fmaf(dkx[r], SPLIT_INV, dk[r]); dv[r] = __builtin_fmaf(dvx[r], SPLIT_INV, dv[r]); }
             }
         }
         // the tile's dK / dV rows: lane = key, registers = d rows (r & 3) + 8 (r >> 2) + 4 h -> four 16-B runs per lane
@@ -890,7 +875,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int d = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int d = mfma32_row(r, h);
             red[wv][32 * j + l32][d] = dq[j][r];
         }
     __syncthreads();

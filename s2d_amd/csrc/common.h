@@ -16,6 +16,10 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// C layout of the 32x32 MFMAs: the tile row that accumulator register r (0..15) holds in lane half h (lane >> 5); the column is lane & 31.
+// `base` (the tile's first row) is added first, term by term from the left: the sum the kernels were compiled with
+__device__ __forceinline__ int mfma32_row(int r, int h, int base = 0) { return base + (r & 3) + 8 * (r >> 2) + 4 * h; }
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies per DEVICE: a process that drives several GPUs must set it on each, so the
 // launchers' "already set" state is a bit per device of the calling thread's current device (atomic: host threads may race to set it)
 #include <atomic>

@@ -26,7 +26,7 @@
 // Schedule of chunk p (one barrier per chunk, weights double-buffered): DMA of the next pieces; GEMM 1 of chunk p (48 MFMAs, the Philox
 // rounds of its mask in their shadow); GEMM 2 k-step 1 of chunk p-1 (24 MFMAs, ReLU / mask / split of chunk p's k-step 0 in their
 // shadow); GEMM 2 k-step 0 of chunk p (24 MFMAs, the same for its k-step 1).
-#include "common.h"
+#include "split_f16.h"
 #include "dropout.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -63,11 +63,6 @@ extern "C" int s2d_ffn_dbg_stamps(unsigned long long *host_out)
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 h16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int FC = 256;                     // model width (the register layout is built on it)
 constexpr int FRAG = 1024;                  // bytes of one MFMA operand fragment (64 lanes x 16 B)
 constexpr int PART = 32 * FRAG;             // 32 KB: 16 k-steps x (hi, lo)  |  8 tiles x 2 k-steps x (hi, lo)
@@ -82,15 +77,6 @@ constexpr int LDS_LN = LDS_PB + FC * 4;     // LayerNorm parameters: gamma1 | be
 // MFMA row rho of a 32-row tile <-> unit / column 16 h + 4 g + i   (rho = 8 g + 4 h + i): a lane half's 16 accumulator registers
 // (reg = 4 g + i at rows 8 g + 4 h + i) are then the 16 consecutive units 16 h + reg
 __host__ __device__ __forceinline__ int perm_row(int rho) { return 16 * ((rho >> 2) & 1) + 4 * (rho >> 3) + (rho & 3); }
-
-__device__ __forceinline__ unsigned int pk_hi(float a, float b) { return __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_pkrtz(a, b)); }
-__device__ __forceinline__ unsigned int pk_lo(float a, float b, unsigned int hi)
-{
-    // (a - h) * 2048 == fma(h, -2048, a * 2048) exactly (a - h is exact, the factor a power of two): one multiply and one
-    // v_fma_mix_f32 (the fp16 operand converted inside the fma) per value instead of convert, subtract, multiply
-    const h16x2 h = __builtin_bit_cast(h16x2, hi);
-    return __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)h[0], -2048.f, a * 2048.f), __builtin_fmaf((float)h[1], -2048.f, b * 2048.f)));
-}
 
 // Register classes.  The 256 output accumulators must live in the accumulator half of the register file and everything else in the
 // vector half (X fragments 128, chunk accumulators 32, activation / weight fragments 48, Philox state ...).  With every MFMA a builtin
@@ -165,8 +151,8 @@ __global__ __launch_bounds__(256) void ffn_pack_kernel(const float *__restrict__
     u32x4 w;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const unsigned int hi = pk_hi(src[2 * q], src[2 * q + 1]);
-        w[q] = lo ? pk_lo(src[2 * q], src[2 * q + 1], hi) : hi;
+        const unsigned int hi = split2_hi(src[2 * q], src[2 * q + 1]);
+        w[q] = lo ? split2_lo_fma(src[2 * q], src[2 * q + 1], hi) : hi;
     }
     out[gid] = w;
 }
@@ -313,8 +299,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const float a = src[t][8 * s2 + 2 * q], b = src[t][8 * s2 + 2 * q + 1];
-                    hi[q] = pk_hi(a, b);
-                    lo[q] = pk_lo(a, b, hi[q]);
+                    hi[q] = split2_hi(a, b);
+                    lo[q] = split2_lo_fma(a, b, hi[q]);
                 }
                 xh[2 * t + s2] = __builtin_bit_cast(f16x8, hi);
                 xl[2 * t + s2] = __builtin_bit_cast(f16x8, lo);
@@ -367,7 +353,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 constexpr int T = decltype(t_)::value;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    float v = __builtin_fmaf(x[4 * q + e], 1.0f / 2048.0f, m[4 * q + e]);
+                    float v = __builtin_fmaf(x[4 * q + e], SPLIT_INV, m[4 * q + e]);      // join_fma (split_f16.h) written out
                     if (DROP) v *= ((mk[q] >> (8 * e)) & 0xFFu) >= p.thresh ? p.dscale : 0.f;     // element 4 q + e of the tile's 16: byte e of word q
                     ym[T][4 * q + e] += v;
                 }
@@ -485,8 +471,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     auto hquarter = [&](int s, int idx) {
         const int q = idx >> 2, part = idx & 3, r0 = 8 * s + 2 * q;
         if (part == 0) {
-            hv0 = fmaxf(__builtin_fmaf(ax[r0], 1.0f / 2048.0f, am[r0]), 0.f);
-            hv1 = fmaxf(__builtin_fmaf(ax[r0 + 1], 1.0f / 2048.0f, am[r0 + 1]), 0.f);
+            hv0 = fmaxf(join_fma(am[r0], ax[r0]), 0.f);
+            hv1 = fmaxf(join_fma(am[r0 + 1], ax[r0 + 1]), 0.f);
         } else if (part == 1) {
             if (DROP) {
                 const uint32_t w = rb[2 * s + (q >> 1)];                // units 8 s + 2 q, + 1 of the lane's 16: bytes 2 (q & 1), + 1 of word 2 s + (q >> 1)
@@ -494,10 +480,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 hv1 *= ((w >> (16 * (q & 1) + 8)) & 0xFFu) >= p.thresh ? p.dscale : 0.f;  // the latter compiles to exec-masked blocks that cut the schedule
             }
         } else if (part == 2) {
-            hhi = pk_hi(hv0, hv1);
+            hhi = split2_hi(hv0, hv1);
             hw[s][q] = hhi;
         } else {
-            lw[s][q] = pk_lo(hv0, hv1, hhi);
+            lw[s][q] = split2_lo_fma(hv0, hv1, hhi);
         }
     };
     // the 16 pieces a wave copies per chunk, all behind the chunk's barrier (which frees their destinations):
@@ -664,7 +650,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int r = 4 * q + e;
-                    x[e] = (dbg & 64) ? 0.f : __builtin_fmaf((float)xl[2 * t + (r >> 3)][r & 7], 1.0f / 2048.0f, (float)xh[2 * t + (r >> 3)][r & 7]);
+                    x[e] = (dbg & 64) ? 0.f : join_fma((float)xh[2 * t + (r >> 3)][r & 7], (float)xl[2 * t + (r >> 3)][r & 7]);
                 }
             }
             if (LN1 && !PRE && S2D_FFN_EPI != 1) {
@@ -675,7 +661,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int r = 4 * q + e;
-                float v = ym[t][r] + yx[t][r] * (1.0f / 2048.0f);
+                float v = join(ym[t][r], yx[t][r]);
                 if (DROP) v = ((m0[q] >> (8 * e)) & 0xFFu) >= p.thresh ? v * p.dscale : 0.f;      // r = 4 q + e: byte e of word q
                 v += x[e];
                 ym[t][r] = v;
@@ -738,8 +724,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int q = 0; q < 4; ++q) pos4[q] = *reinterpret_cast<const f32x4 *>((haspos ? posr : pbr) + 32 * j + 4 * q);
         };
         auto tile_out = [&](const f32x16 &m, const f32x16 &x, int j, int q) {
-            f32x4 v = {m[4 * q] + x[4 * q] * (1.0f / 2048.0f), m[4 * q + 1] + x[4 * q + 1] * (1.0f / 2048.0f),
-                       m[4 * q + 2] + x[4 * q + 2] * (1.0f / 2048.0f), m[4 * q + 3] + x[4 * q + 3] * (1.0f / 2048.0f)};
+            f32x4 v = {join(m[4 * q], x[4 * q]), join(m[4 * q + 1], x[4 * q + 1]),
+                       join(m[4 * q + 2], x[4 * q + 2]), join(m[4 * q + 3], x[4 * q + 3])};
             v += pos4[q];
             if (!(dbg & 32)) *reinterpret_cast<f32x4 *>(outr + 32 * j + 4 * q) = v;        // unconditional (rows past M rewrite row M - 1 with its own values): the wait below counts it
         };

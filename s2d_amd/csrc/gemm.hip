@@ -10,8 +10,7 @@
 // global loads fly under the current tile's 64 MFMAs per wave.  Each lane feeds four consecutive MFMAs
 // from one ds_read_b128: lane half h supplies k = 8g+4h+j for MFMA j of group g (A and B use the same
 // map, so every k is visited once).
-#include "common.h"
-#include "gemm_params.h"
+#include "gemm_epilogue.h"
 #include "dropout.h"
 
 namespace {
@@ -156,12 +155,9 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmParams p)
         for (int tm = 0; tm < 2; ++tm) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int row = mfma32_row(r, h, m0 + wm * 64 + tm * 32);
                 if (row >= p.M) continue;
-                float v = acc[tm][tn][r] * sc + bi;
-                if (res && col < p.res_cols) v += res[(long)(p.res_rows ? row % p.res_rows : row) * p.ldr + col];
-                if (p.relu) v = fmaxf(v, 0.f);
-                C[(long)row * p.ldc + col] = v;
+                C[(long)row * p.ldc + col] = scalar_tail(p, res, acc[tm][tn][r], sc, bi, row, col);
             }
         }
     }

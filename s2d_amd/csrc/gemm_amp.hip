@@ -12,8 +12,7 @@
 // four waves of 64 x 64 (2 x 2 MFMA tiles x 4 k-steps), two workgroups per CU.  Staging: global f32 (16-B loads, hardware
 // bounds) -> registers (one k-tile ahead) -> v_cvt (RTN) -> LDS rows of [32 words = 64 halves | 4 pad] (the 36-word row of
 // gemm_bf16.hip: conflict-free ds_read_b128 fragment reads), double buffered, one barrier per k-tile.
-#include "common.h"
-#include "gemm_params.h"
+#include "gemm_epilogue.h"
 
 namespace {
 
@@ -154,7 +153,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_amp_kernel(GemmParams p)
 #pragma unroll
             for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) ep[(tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 68 + tn * 32 + l32] = acc[tm][tn][r];
+                for (int r = 0; r < 16; ++r) ep[mfma32_row(r, h, tm * 32) * 68 + tn * 32 + l32] = acc[tm][tn][r];
         const int c4 = lane & 15, rr = lane >> 4;
         const int col = n0 + wn * 64 + c4 * 4;
         if (col < p.N) {
@@ -167,9 +166,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_amp_kernel(GemmParams p)
                 const int row = rbase + it * 4;
                 if (row >= p.M) break;
                 f32x4 v = *reinterpret_cast<const f32x4 *>(&ep[(it * 4 + rr) * 68 + c4 * 4]);
-                v = v * sc + bi;
-                if (res && col < p.res_cols) v += *reinterpret_cast<const f32x4 *>(res + (long)(p.res_rows ? row % p.res_rows : row) * p.ldr + col);
-                if (p.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+                v = row_tail<false>(p, res, v, sc, bi, row, col);
                 *reinterpret_cast<f32x4 *>(C + (long)row * p.ldc + col) = v;
             }
         }
@@ -185,12 +182,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_amp_kernel(GemmParams p)
         for (int tm = 0; tm < 2; ++tm) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int row = mfma32_row(r, h, m0 + wm * 64 + tm * 32);
                 if (row >= p.M) continue;
-                float v = acc[tm][tn][r] * sc + bi;
-                if (res && col < p.res_cols) v += res[(long)(p.res_rows ? row % p.res_rows : row) * p.ldr + col];
-                if (p.relu) v = fmaxf(v, 0.f);
-                C[(long)row * p.ldc + col] = v;
+                C[(long)row * p.ldc + col] = scalar_tail(p, res, acc[tm][tn][r], sc, bi, row, col);
             }
         }
     }

@@ -11,8 +11,7 @@
 // threads, 1 workgroup/CU = 2 waves/SIMD) for large M, WM = 2 (128x128) otherwise.  Staging: global f32 (16-B loads)
 // -> registers -> split (v_cvt_pk_bf16_f32, v_pk_add_f32) -> LDS rows of [16 words hi | 16 words lo | 4 pad]
 // (stride 36 words: conflict-free for ds_read_b128 fragment reads and the ds_write_b64 stores), double buffered.
-#include "common.h"
-#include "gemm_params.h"
+#include "gemm_epilogue.h"
 #include "dropout.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -21,13 +20,10 @@ namespace {
 
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4_t __attribute__((vector_size(16)));
 
 constexpr int BN = 128, BK = 32, ROWW = 36;  // LDS row = 36 words (144 B)
 
-__device__ __forceinline__ void split4(const f32x4 v, u32x2 &hi, u32x2 &lo)
+__device__ __forceinline__ void split4_bf16(const f32x4 v, u32x2 &hi, u32x2 &lo)
 {
     const f32x2 a = {v[0], v[1]}, b = {v[2], v[3]};
     const bf16x2 ha = __builtin_convertvector(a, bf16x2), hb = __builtin_convertvector(b, bf16x2);
@@ -133,7 +129,7 @@ __global__ __launch_bounds__(128 * WM, 1) void gemm_bf16x3_kernel(GemmParams p)
 #pragma unroll
         for (int i = 0; i < A_IT; ++i) {
             u32x2 hi, lo;
-            split4(ra[i], hi, lo);
+            split4_bf16(ra[i], hi, lo);
             unsigned int *row = &As[(buf * BM + r0 + RPT * i) * ROWW];
             *reinterpret_cast<u32x2 *>(row + c4 * 2) = hi;
             *reinterpret_cast<u32x2 *>(row + 16 + c4 * 2) = lo;
@@ -141,7 +137,7 @@ __global__ __launch_bounds__(128 * WM, 1) void gemm_bf16x3_kernel(GemmParams p)
 #pragma unroll
         for (int i = 0; i < B_IT; ++i) {
             u32x2 hi, lo;
-            split4(rb[i], hi, lo);
+            split4_bf16(rb[i], hi, lo);
             unsigned int *row = &Bs[(buf * BN + r0 + RPT * i) * ROWW];
             *reinterpret_cast<u32x2 *>(row + c4 * 2) = hi;
             *reinterpret_cast<u32x2 *>(row + 16 + c4 * 2) = lo;
@@ -212,12 +208,9 @@ __global__ __launch_bounds__(128 * WM, 1) void gemm_bf16x3_kernel(GemmParams p)
         for (int tm = 0; tm < 2; ++tm) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int row = mfma32_row(r, h, m0 + wm * 64 + tm * 32);
                 if (row >= p.M) continue;
-                float v = acc[tm][tn][r] * sc + bi;
-                if (res && col < p.res_cols) v += res[(long)(p.res_rows ? row % p.res_rows : row) * p.ldr + col];
-                if (p.relu) v = fmaxf(v, 0.f);
-                C[(long)row * p.ldc + col] = v;
+                C[(long)row * p.ldc + col] = scalar_tail(p, res, acc[tm][tn][r], sc, bi, row, col);
             }
         }
     }
@@ -321,7 +314,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_w128_kernel(GemmParams p)
 #pragma unroll
         for (int i = 0; i < A_IT; ++i) {
             u32x2 hi, lo;
-            split4(ra[i], hi, lo);
+            split4_bf16(ra[i], hi, lo);
             unsigned int *row = &As[(r0 + RPT * i) * ROWW];
             *reinterpret_cast<u32x2 *>(row + c4 * 2) = hi;
             *reinterpret_cast<u32x2 *>(row + 16 + c4 * 2) = lo;
@@ -331,7 +324,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_w128_kernel(GemmParams p)
             u32x2 hi, lo;
             unsigned int *row = &Bs[(r0 + RPT * i) * ROWW];
             if (BSPLIT) { *reinterpret_cast<f32x4 *>(row + wsel) = rb[i]; continue; }
-            split4(rb[i], hi, lo);
+            split4_bf16(rb[i], hi, lo);
             *reinterpret_cast<u32x2 *>(row + c4 * 2) = hi;
             *reinterpret_cast<u32x2 *>(row + 16 + c4 * 2) = lo;
         }
@@ -402,7 +395,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_w128_kernel(GemmParams p)
                 for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        ep[(tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 68 + tn * 32 + l32] = acc[half * 2 + tm][tn][r];
+                        ep[mfma32_row(r, h, tm * 32) * 68 + tn * 32 + l32] = acc[half * 2 + tm][tn][r];
             const int c4e = lane & 15, rr = lane >> 4;
             const int col = n0 + wn * 64 + c4e * 4;
             if (col < p.N) {
@@ -415,9 +408,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_w128_kernel(GemmParams p)
                     const int row = rbase + it * 4;
                     if (row >= p.M) break;
                     f32x4 v = *reinterpret_cast<const f32x4 *>(&ep[(it * 4 + rr) * 68 + c4e * 4]);
-                    v = v * sc + bi;
-                    if (res && col < p.res_cols) v += *reinterpret_cast<const f32x4 *>(res + (long)(p.res_rows ? row % p.res_rows : row) * p.ldr + col);
-                    if (p.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+                    v = row_tail<false>(p, res, v, sc, bi, row, col);
                     *reinterpret_cast<f32x4 *>(C + (long)row * p.ldc + col) = v;
                 }
             }
@@ -432,12 +423,9 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_w128_kernel(GemmParams p)
                 for (int tm = 0; tm < 2; ++tm) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int row = m0 + wm * 128 + half * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                        const int row = mfma32_row(r, h, m0 + wm * 128 + half * 64 + tm * 32);
                         if (row >= p.M) continue;
-                        float v = acc[half * 2 + tm][tn][r] * sc + bi;
-                        if (res && col < p.res_cols) v += res[(long)(p.res_rows ? row % p.res_rows : row) * p.ldr + col];
-                        if (p.relu) v = fmaxf(v, 0.f);
-                        C[(long)row * p.ldc + col] = v;
+                        C[(long)row * p.ldc + col] = scalar_tail(p, res, acc[half * 2 + tm][tn][r], sc, bi, row, col);
                     }
                 }
             }
@@ -446,25 +434,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_w128_kernel(GemmParams p)
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Split-fp16 x3 with a scaled low part ("f16x3"): fp32-class accuracy (~3*2^-22) at the same MFMA count.
-//   x = h + l * 2^-11,   h = fp16_rtz(x),   l = fp16_rtz((x - h) * 2^11)          (22+ significant bits while h is a
-//   A.B^T = [Ah.Bh^T] + 2^-11 * [Ah.Bl^T + Al.Bh^T]                                 normal fp16 number, |x| >= 2^-14)
-// The two brackets are accumulated in separate f32 accumulators (main / cross) and combined in the epilogue.
-// The accuracy window is an operand amax in [2^-14, 65504]: below it h is subnormal or zero and l loses bits too (the error grows
-// ~10x per decade of scale), above it the RTZ conversion saturates (x -> 65535.98, no inf).  The forward's activations and weights
-// are O(1e-3..1e3); the gradients are brought into the window by the backward's power-of-two root scale (backward.grad_scale).
-typedef __fp16 h16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void split4_f16(const f32x4 v, u32x2 &hi, u32x2 &lo)
-{
-    const h16x2 ha = __builtin_amdgcn_cvt_pkrtz(v[0], v[1]), hb = __builtin_amdgcn_cvt_pkrtz(v[2], v[3]);
-    const f32x2 a = {v[0], v[1]}, b = {v[2], v[3]};
-    const f32x2 ra = (a - __builtin_convertvector(ha, f32x2)) * 2048.f, rb = (b - __builtin_convertvector(hb, f32x2)) * 2048.f;
-    const h16x2 la = __builtin_amdgcn_cvt_pkrtz(ra[0], ra[1]), lb = __builtin_amdgcn_cvt_pkrtz(rb[0], rb[1]);
-    hi[0] = __builtin_bit_cast(unsigned int, ha); hi[1] = __builtin_bit_cast(unsigned int, hb);
-    lo[0] = __builtin_bit_cast(unsigned int, la); lo[1] = __builtin_bit_cast(unsigned int, lb);
-}
+// Split-fp16 x3 with a scaled low part ("f16x3", split_f16.h): main and cross accumulators, joined in the epilogue.
 
 template <bool CONV, bool PIPE, bool BSPLIT, bool DROP = false>
 __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(GemmParams p)
@@ -549,13 +519,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(GemmParams p)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             u32x2 hi, lo;
-            split4_f16(ra[i], hi, lo);
+            split4(ra[i], hi, lo);
             unsigned int *row = &As[(buf * BM + r0 + RPT * i) * ROWW];
             *reinterpret_cast<u32x2 *>(row + c4 * 2) = hi;
             *reinterpret_cast<u32x2 *>(row + 16 + c4 * 2) = lo;
             row = &Bs[(buf * BN + r0 + RPT * i) * ROWW];
             if (BSPLIT) { *reinterpret_cast<f32x4 *>(row + wsel) = rb[i]; continue; }
-            split4_f16(rb[i], hi, lo);
+            split4(rb[i], hi, lo);
             *reinterpret_cast<u32x2 *>(row + c4 * 2) = hi;
             *reinterpret_cast<u32x2 *>(row + 16 + c4 * 2) = lo;
         }
@@ -617,13 +587,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(GemmParams p)
         };
         auto store_slot = [&](int buf, int i) {
             u32x2 hi, lo;
-            split4_f16(ra[i], hi, lo);
+            split4(ra[i], hi, lo);
             unsigned int *row = &As[(buf * BM + r0 + RPT * i) * ROWW];
             *reinterpret_cast<u32x2 *>(row + c4 * 2) = hi;
             *reinterpret_cast<u32x2 *>(row + 16 + c4 * 2) = lo;
             row = &Bs[(buf * BN + r0 + RPT * i) * ROWW];
             if (BSPLIT) { *reinterpret_cast<f32x4 *>(row + wsel) = rb[i]; return; }
-            split4_f16(rb[i], hi, lo);
+            split4(rb[i], hi, lo);
             *reinterpret_cast<u32x2 *>(row + c4 * 2) = hi;
             *reinterpret_cast<u32x2 *>(row + 16 + c4 * 2) = lo;
         };
@@ -670,18 +640,18 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(GemmParams p)
                 if (g == 0) read_a(0, 1, 1);
                 if (g == 1) { read_b(1); read_a(1, 0, 0); }
                 if (g == 2) read_a(1, 1, 1);
-                ha0 = __builtin_amdgcn_cvt_pkrtz(va[0], va[1]); ha1 = __builtin_amdgcn_cvt_pkrtz(va[2], va[3]);
+                ha0 = split_hi(va[0], va[1]); ha1 = split_hi(va[2], va[3]);
                 __builtin_amdgcn_sched_barrier(0);
                 // chunk 1   (dependent MFMAs on one accumulator are kept two chunks apart)
                 accx[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[fs], bh[s][1], accx[i][1], 0, 0, 0);
-                fa0 = __builtin_convertvector(ha0, f32x2); fa1 = __builtin_convertvector(ha1, f32x2);
+                fa0 = split_hi_f32(ha0); fa1 = split_hi_f32(ha1);
                 __builtin_amdgcn_sched_barrier(0);
                 // chunk 2
                 accm[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[fs], bh[s][0], accm[i][0], 0, 0, 0);
                 {
                     const f32x2 a0 = {va[0], va[1]}, a1 = {va[2], va[3]};
-                    const f32x2 r0_ = (a0 - fa0) * 2048.f, r1_ = (a1 - fa1) * 2048.f;
-                    const h16x2 l0 = __builtin_amdgcn_cvt_pkrtz(r0_[0], r0_[1]), l1 = __builtin_amdgcn_cvt_pkrtz(r1_[0], r1_[1]);
+                    const f32x2 r0_ = split_rem(a0, fa0), r1_ = split_rem(a1, fa1);
+                    const h16x2 l0 = split_lo(r0_), l1 = split_lo(r1_);
                     const u32x2 hi = {__builtin_bit_cast(unsigned int, ha0), __builtin_bit_cast(unsigned int, ha1)};
                     const u32x2 lo = {__builtin_bit_cast(unsigned int, l0), __builtin_bit_cast(unsigned int, l1)};
                     *reinterpret_cast<u32x2 *>(rowA + c4 * 2) = hi;
@@ -692,16 +662,16 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(GemmParams p)
                 accx[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[fs], bl[s][0], accx[i][0], 0, 0, 0);
                 if (BSPLIT) *reinterpret_cast<f32x4 *>(rowB + wsel) = vb;
                 else {
-                    hb0 = __builtin_amdgcn_cvt_pkrtz(vb[0], vb[1]); hb1 = __builtin_amdgcn_cvt_pkrtz(vb[2], vb[3]);
-                    fb0 = __builtin_convertvector(hb0, f32x2); fb1 = __builtin_convertvector(hb1, f32x2);
+                    hb0 = split_hi(vb[0], vb[1]); hb1 = split_hi(vb[2], vb[3]);
+                    fb0 = split_hi_f32(hb0); fb1 = split_hi_f32(hb1);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 // chunk 4
                 accx[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[fs], bl[s][1], accx[i][1], 0, 0, 0);
                 if (!BSPLIT) {
                     const f32x2 b0 = {vb[0], vb[1]}, b1 = {vb[2], vb[3]};
-                    const f32x2 r0_ = (b0 - fb0) * 2048.f, r1_ = (b1 - fb1) * 2048.f;
-                    const h16x2 l0 = __builtin_amdgcn_cvt_pkrtz(r0_[0], r0_[1]), l1 = __builtin_amdgcn_cvt_pkrtz(r1_[0], r1_[1]);
+                    const f32x2 r0_ = split_rem(b0, fb0), r1_ = split_rem(b1, fb1);
+                    const h16x2 l0 = split_lo(r0_), l1 = split_lo(r1_);
                     const u32x2 hi = {__builtin_bit_cast(unsigned int, hb0), __builtin_bit_cast(unsigned int, hb1)};
                     const u32x2 lo = {__builtin_bit_cast(unsigned int, l0), __builtin_bit_cast(unsigned int, l1)};
                     *reinterpret_cast<u32x2 *>(rowB + c4 * 2) = hi;
@@ -761,8 +731,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(GemmParams p)
             for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    ep[(tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 68 + tn * 32 + l32] =
-                        accm[tm][tn][r] + accx[tm][tn][r] * (1.0f / 2048.0f);
+                    ep[mfma32_row(r, h, tm * 32) * 68 + tn * 32 + l32] = join(accm[tm][tn][r], accx[tm][tn][r]);
         if constexpr (DROP) {
             // dropout epilogue: a lane owns one 8-column mask block of a row (one Philox call), 8 lanes x 32 B = a 256-B row
             // segment per instruction, 8 rows per pass.  act(drop(acc * scale + bias) + res): the mask multiplies by 0 or 1 / (1 - p).
@@ -810,14 +779,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(GemmParams p)
                 const int row = rbase + it * 4;
                 if (row >= p.M) break;
                 f32x4 v = *reinterpret_cast<const f32x4 *>(&ep[(it * 4 + rr) * 68 + c4 * 4]);
-                v = v * sc + bi;
-                if (res && col < p.res_cols) v += *reinterpret_cast<const f32x4 *>(res + (long)(p.res_rows ? row % p.res_rows : row) * p.ldr + col);
-                if (p.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-                if (p.gate) {
-                    const f32x4 g = *reinterpret_cast<const f32x4 *>(p.gate + (long)row * p.ldg + col);
-                    v[0] = g[0] > 0.f ? v[0] * p.gate_scale : 0.f; v[1] = g[1] > 0.f ? v[1] * p.gate_scale : 0.f;
-                    v[2] = g[2] > 0.f ? v[2] * p.gate_scale : 0.f; v[3] = g[3] > 0.f ? v[3] * p.gate_scale : 0.f;
-                }
+                v = row_tail<true>(p, res, v, sc, bi, row, col);
                 *reinterpret_cast<f32x4 *>(C + (long)row * p.ldc + col) = v;
             }
         }
@@ -833,12 +795,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(GemmParams p)
         for (int tm = 0; tm < 2; ++tm) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int row = mfma32_row(r, h, m0 + wm * 64 + tm * 32);
                 if (row >= p.M) continue;
-                float v = (accm[tm][tn][r] + accx[tm][tn][r] * (1.0f / 2048.0f)) * sc + bi;
-                if (res && col < p.res_cols) v += res[(long)(p.res_rows ? row % p.res_rows : row) * p.ldr + col];
-                if (p.relu) v = fmaxf(v, 0.f);
-                C[(long)row * p.ldc + col] = v;
+                C[(long)row * p.ldc + col] = scalar_tail(p, res, join(accm[tm][tn][r], accx[tm][tn][r]), sc, bi, row, col);
             }
         }
     }
@@ -924,7 +883,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_halo_kernel(GemmParams p
         for (int i = 0; i < A_IT; ++i) {
             if (ha_dst[i] < 0) continue;
             u32x2 hi, lo;
-            split4_f16(ra[i], hi, lo);
+            split4(ra[i], hi, lo);
             if (ha_zero[i]) { hi = u32x2{0u, 0u}; lo = u32x2{0u, 0u}; }
             *reinterpret_cast<u32x2 *>(Ah + ha_dst[i]) = hi;
             *reinterpret_cast<u32x2 *>(Ah + ha_dst[i] + 16) = lo;
@@ -1063,7 +1022,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_halo_kernel(GemmParams p
         for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                ep[(tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 68 + tn * 32 + l32] = accm[tm][tn][r] + accx[tm][tn][r] * (1.0f / 2048.0f);
+                ep[mfma32_row(r, h, tm * 32) * 68 + tn * 32 + l32] = join(accm[tm][tn][r], accx[tm][tn][r]);
     const int c4e = lane & 15, rr = lane >> 4;
     const int col = n0 + wn * 64 + c4e * 4;
     if (col < p.N) {
@@ -1079,7 +1038,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_halo_kernel(GemmParams p
             f32x4 v = *reinterpret_cast<const f32x4 *>(&ep[(it * 4 + rr) * 68 + c4e * 4]);
             v = v * sc + bi;
             if (p.res) v += *reinterpret_cast<const f32x4 *>(p.res + row * p.ldr + col);
-            if (p.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+            v = row_act<false>(p, v, row, col);
             *reinterpret_cast<f32x4 *>(p.C + row * p.ldc + col) = v;
         }
     }
@@ -1157,7 +1116,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PH == 16 ? 
         const int item = tid + 256 * i;
         if (item >= ST_HH * ST_HW) continue;
         u32x2 hi, lo;
-        split4_f16(ra[i], hi, lo);
+        split4(ra[i], hi, lo);
         *reinterpret_cast<u32x2 *>(Ah + item * 2) = hi;
         *reinterpret_cast<u32x2 *>(Al + item * 2) = lo;
     }
@@ -1196,11 +1155,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PH == 16 ? 
             }
 #pragma unroll
             for (int i = 0; i < RT; ++i) {
-                typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
                 const u32x2 h0 = *reinterpret_cast<const u32x2 *>(Ah + a_pix[i] + oa), h1 = *reinterpret_cast<const u32x2 *>(Ah + a_pix[i] + ob);
                 const u32x2 l0 = *reinterpret_cast<const u32x2 *>(Al + a_pix[i] + oa), l1 = *reinterpret_cast<const u32x2 *>(Al + a_pix[i] + ob);
-                const f16x8 ah = __builtin_bit_cast(f16x8, u32x4v{h0[0], h0[1], h1[0], h1[1]});
-                const f16x8 al = __builtin_bit_cast(f16x8, u32x4v{l0[0], l0[1], l1[0], l1[1]});
+                const f16x8 ah = __builtin_bit_cast(f16x8, u32x4{h0[0], h0[1], h1[0], h1[1]});
+                const f16x8 al = __builtin_bit_cast(f16x8, u32x4{l0[0], l0[1], l1[0], l1[1]});
                 accx[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[0], accx[i][0], 0, 0, 0);
                 accx[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[1], accx[i][1], 0, 0, 0);
                 accx[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[0], accx[i][0], 0, 0, 0);
@@ -1220,7 +1178,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PH == 16 ? 
         for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                ep[(tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 68 + tn * 32 + l32] = accm[tm][tn][r] + accx[tm][tn][r] * (1.0f / 2048.0f);
+                ep[mfma32_row(r, h, tm * 32) * 68 + tn * 32 + l32] = join(accm[tm][tn][r], accx[tm][tn][r]);
     const int c4e = lane & 15, rr = lane >> 4;
     const int col = c4e * 4;
     if (col < p.N) {
@@ -1236,7 +1194,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PH == 16 ? 
             f32x4 v = *reinterpret_cast<const f32x4 *>(&ep[(it * 4 + rr) * 68 + c4e * 4]);
             v = v * sc + bi;
             if (p.res) v += *reinterpret_cast<const f32x4 *>(p.res + row * p.ldr + col);
-            if (p.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+            v = row_act<false>(p, v, row, col);
             *reinterpret_cast<f32x4 *>(p.C + row * p.ldc + col) = v;
         }
     }
@@ -1337,7 +1295,7 @@ __global__ __launch_bounds__(256, PRE ? 3 : 4) void gemm_f16x3_hi_kernel(GemmPar
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             u32x2 hi, lo;
-            split4_f16(ra[i], hi, lo);
+            split4(ra[i], hi, lo);
             unsigned int *row = &As[(r0 + RPT * i) * ROWW];
             *reinterpret_cast<u32x2 *>(row + c4 * 2) = hi;
             *reinterpret_cast<u32x2 *>(row + 16 + c4 * 2) = lo;
@@ -1347,7 +1305,7 @@ __global__ __launch_bounds__(256, PRE ? 3 : 4) void gemm_f16x3_hi_kernel(GemmPar
             u32x2 hi, lo;
             unsigned int *row = &Bs[(r0 + RPT * i) * ROWW];
             if (BSPLIT) { *reinterpret_cast<f32x4 *>(row + wsel) = rb[i]; continue; }
-            split4_f16(rb[i], hi, lo);
+            split4(rb[i], hi, lo);
             *reinterpret_cast<u32x2 *>(row + c4 * 2) = hi;
             *reinterpret_cast<u32x2 *>(row + 16 + c4 * 2) = lo;
         }
@@ -1401,7 +1359,7 @@ __global__ __launch_bounds__(256, PRE ? 3 : 4) void gemm_f16x3_hi_kernel(GemmPar
         for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                ep[(tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 36 + l32] = accm[tm][r] + accx[tm][r] * (1.0f / 2048.0f);
+                ep[mfma32_row(r, h, tm * 32) * 36 + l32] = join(accm[tm][r], accx[tm][r]);
         const int c4e = lane & 7, rr = lane >> 3;                         // 8 lanes x 16 B = one 128-B row segment
         const int col = n0 + wn * 32 + c4e * 4;
         if (col < p.N) {
@@ -1414,6 +1372,7 @@ __global__ __launch_bounds__(256, PRE ? 3 : 4) void gemm_f16x3_hi_kernel(GemmPar
                 const int row = rbase + it * 8;
                 if (row >= p.M) break;
                 f32x4 v = *reinterpret_cast<const f32x4 *>(&ep[(it * 8 + rr) * 36 + c4e * 4]);
+                // row_tail (gemm_epilogue.h) written out: PRE's residual is already in registers
                 v = v * sc + bi;
                 if constexpr (PRE) v += rres[it];
                 else if (res && col < p.res_cols) v += *reinterpret_cast<const f32x4 *>(res + (long)(p.res_rows ? row % p.res_rows : row) * p.ldr + col);
@@ -1436,12 +1395,9 @@ __global__ __launch_bounds__(256, PRE ? 3 : 4) void gemm_f16x3_hi_kernel(GemmPar
     for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = m0 + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int row = mfma32_row(r, h, m0 + wm * 64 + tm * 32);
             if (row >= p.M) continue;
-            float v = (accm[tm][r] + accx[tm][r] * (1.0f / 2048.0f)) * sc + bi;
-            if (res && col < p.res_cols) v += res[(long)(p.res_rows ? row % p.res_rows : row) * p.ldr + col];
-            if (p.relu) v = fmaxf(v, 0.f);
-            C[(long)row * p.ldc + col] = v;
+            C[(long)row * p.ldc + col] = scalar_tail(p, res, join(accm[tm][r], accx[tm][r]), sc, bi, row, col);
         }
 }
 
@@ -1548,8 +1504,8 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x3_ws_kernel(GemmParams p)
                     for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
-                            ep[(tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 68 + tn * 32 + l32] =
-                                accm[tm][tn][r] + accx[tm][tn][r] * (1.0f / 2048.0f);
+                            ep[mfma32_row(r, h, tm * 32) * 68 + tn * 32 + l32] =
+                                join(accm[tm][tn][r], accx[tm][tn][r]);
                             accm[tm][tn][r] = 0.f; accx[tm][tn][r] = 0.f;
                         }
             }
@@ -1652,14 +1608,14 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x3_ws_kernel(GemmParams p)
             unsigned int *row = &As[(r0 + RPT * i) * ROWW];
             if (ASPLIT) *reinterpret_cast<f32x4 *>(row + wsel) = ra[i];
             else {
-                split4_f16(ra[i], hi, lo);
+                split4(ra[i], hi, lo);
                 if (CONV && ((zm >> i) & 1u)) { hi = u32x2{0u, 0u}; lo = u32x2{0u, 0u}; }
                 *reinterpret_cast<u32x2 *>(row + c4 * 2) = hi;
                 *reinterpret_cast<u32x2 *>(row + 16 + c4 * 2) = lo;
             }
             row = &Bs[(r0 + RPT * i) * ROWW];
             if (BSPLIT) { *reinterpret_cast<f32x4 *>(row + wsel) = rb[i]; continue; }
-            split4_f16(rb[i], hi, lo);
+            split4(rb[i], hi, lo);
             *reinterpret_cast<u32x2 *>(row + c4 * 2) = hi;
             *reinterpret_cast<u32x2 *>(row + 16 + c4 * 2) = lo;
         }
@@ -1774,7 +1730,7 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x3_ws_kernel(GemmParams p)
             if (cok && row < p.M) {
 #pragma unroll
                 for (int w = 0; w < EV; ++w)
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v[c][w]), rsC, (int)s.coff, it * ldc4 + 16 * w, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v[c][w]), rsC, (int)s.coff, it * ldc4 + 16 * w, 0);
             }
         }
     };
@@ -2050,8 +2006,8 @@ __global__ __launch_bounds__(256) void split_weights_kernel(const float *__restr
         }
     }
     u32x2 hi, lo;
-    if (BF16) split4(v, hi, lo);            // split-bf16 mode: unscaled low part (gemm_bf16x3_w128_kernel)
-    else split4_f16(v, hi, lo);
+    if (BF16) split4_bf16(v, hi, lo);            // split-bf16 mode: unscaled low part (gemm_bf16x3_w128_kernel)
+    else split4(v, hi, lo);
     unsigned int *o = out + nb * 32;
     *reinterpret_cast<u32x2 *>(o + c4 * 2) = hi;
     *reinterpret_cast<u32x2 *>(o + 16 + c4 * 2) = lo;

@@ -9,37 +9,12 @@
 // wave order through LDS (fixed order: reproducible) before the usual epilogue (scale, bias, residual, ReLU).
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "split_f16.h"
 #include "gemm_params.h"
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __fp16 h16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int TM = 32, TN = 64, RS = 72;      // RS: LDS row stride of a partial tile (rows 4 apart land 32 banks apart)
-
-// x = h + l * 2^-11, h = fp16_rtz(x), l = fp16_rtz((x - h) * 2^11): the same split as gemm_bf16.hip's split4_f16
-__device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, f16x8 &hi, f16x8 &lo)
-{
-    u32x4 h, l;
-    const f32x4 v[2] = {a, b};
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const h16x2 h0 = __builtin_amdgcn_cvt_pkrtz(v[i][0], v[i][1]), h1 = __builtin_amdgcn_cvt_pkrtz(v[i][2], v[i][3]);
-        const f32x2 x0 = {v[i][0], v[i][1]}, x1 = {v[i][2], v[i][3]};
-        const f32x2 r0 = (x0 - __builtin_convertvector(h0, f32x2)) * 2048.f, r1 = (x1 - __builtin_convertvector(h1, f32x2)) * 2048.f;
-        const h16x2 l0 = __builtin_amdgcn_cvt_pkrtz(r0[0], r0[1]), l1 = __builtin_amdgcn_cvt_pkrtz(r1[0], r1[1]);
-        h[2 * i] = __builtin_bit_cast(unsigned int, h0); h[2 * i + 1] = __builtin_bit_cast(unsigned int, h1);
-        l[2 * i] = __builtin_bit_cast(unsigned int, l0); l[2 * i + 1] = __builtin_bit_cast(unsigned int, l1);
-    }
-    hi = __builtin_bit_cast(f16x8, h);
-    lo = __builtin_bit_cast(f16x8, l);
-}
 
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void gemm_small_m_kernel(GemmParams p, int kper)
@@ -107,7 +82,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_small_m_kernel(GemmParams p, int
     for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            mine[((r & 3) + 8 * (r >> 2) + 4 * h) * RS + 32 * t + l32] = accm[t][r] + accx[t][r] * (1.0f / 2048.0f);
+            mine[mfma32_row(r, h) * RS + 32 * t + l32] = join(accm[t][r], accx[t][r]);
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < PER; ++j) {

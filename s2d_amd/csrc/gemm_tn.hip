@@ -9,14 +9,10 @@
 // C + s * slice_stride and s2d_reduce_slices_f32 adds the slices in a fixed order (reproducible; the taps of a convolution
 // interleave their partial tiles, slice_stride = taps * Mo * No, so that ONE reduction finishes all of them).  B may start `shift` rows later
 // than A (a convolution tap on the zero-padded grid): rows past its end read as zero.
-#include "common.h"
+#include "split_f16.h"
 #include <stdlib.h>
 
 namespace {
-
-typedef __fp16 h16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int TBK = 32, TROWW = 36;
 constexpr unsigned int TOOB = 0xFFFFFFF0u;
@@ -41,16 +37,6 @@ __device__ __forceinline__ unsigned int div_magic(unsigned int m, unsigned int m
 {
     const unsigned int t = __umulhi(m, magic);
     return (t + ((m - t) >> 1)) >> shift;
-}
-
-// hi / lo fp16 pairs of two values that are consecutive along the contraction
-__device__ __forceinline__ void split_pair(float a, float b, unsigned int &hi, unsigned int &lo)
-{
-    const h16x2 h = __builtin_amdgcn_cvt_pkrtz(a, b);
-    const f32x2 f = __builtin_convertvector(h, f32x2);
-    const h16x2 l = __builtin_amdgcn_cvt_pkrtz((a - f[0]) * 2048.f, (b - f[1]) * 2048.f);
-    hi = __builtin_bit_cast(unsigned int, h);
-    lo = __builtin_bit_cast(unsigned int, l);
 }
 
 // BNs = 128 (outputs at least 128 columns wide): a wave owns 64 x 64 of a 128 x 128 tile -- per 32 contraction rows 24 MFMAs against 8
@@ -135,7 +121,7 @@ __global__ __launch_bounds__(256, BNs == 128 ? 2 : 4) void gemm_tn_f16x3_kernel(
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 unsigned int hi, lo;
-                split_pair(va[2 * i][j], va[2 * i + 1][j], hi, lo);
+                split2(va[2 * i][j], va[2 * i + 1][j], hi, lo);
                 unsigned int *row = &As[(32 * j + ca) * TROWW + ra_ + 8 * i];       // column 4 ca + j lives in LDS row 32 j + ca
                 row[0] = hi; row[16] = lo;
             }
@@ -144,7 +130,7 @@ __global__ __launch_bounds__(256, BNs == 128 ? 2 : 4) void gemm_tn_f16x3_kernel(
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 unsigned int hi, lo;
-                split_pair(vb[2 * i][j], vb[2 * i + 1][j], hi, lo);
+                split2(vb[2 * i][j], vb[2 * i + 1][j], hi, lo);
                 unsigned int *row = &Bs[((BNs / 4) * j + cb) * TROWW + rb_ + 8 * i];    // column 4 cb + j lives in LDS row (BNs / 4) j + cb
                 row[0] = hi; row[16] = lo;
             }
@@ -247,7 +233,7 @@ __global__ __launch_bounds__(256, BNs == 128 ? 2 : 4) void gemm_tn_f16x3_kernel(
                 for (int r = 0; r < 4; ++r) {
                     const int ra = 64 * wm + 16 * i + 4 * kq + r;
                     const int row = m0 + 4 * (ra & 31) + (ra >> 5);
-                    if (row < p.Mo) C[(long)row * ldc + col] = acm[i][t][r] + acx[i][t][r] * (1.0f / 2048.0f);
+                    if (row < p.Mo) C[(long)row * ldc + col] = join(acm[i][t][r], acx[i][t][r]);
                 }
         }
         return;
@@ -261,9 +247,9 @@ __global__ __launch_bounds__(256, BNs == 128 ? 2 : 4) void gemm_tn_f16x3_kernel(
         for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int rr = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int rr = mfma32_row(r, h);
                 const int row = m0 + 4 * rr + 2 * wm + tm;
-                if (row < p.Mo) C[(long)row * ldc + col] = accm[tm][tn][r] + accx[tm][tn][r] * (1.0f / 2048.0f);
+                if (row < p.Mo) C[(long)row * ldc + col] = join(accm[tm][tn][r], accx[tm][tn][r]);
             }
     }
 }

@@ -13,7 +13,7 @@
 //
 // Mask logits are read PIXEL-MAJOR ([T*hm*wm][ldq], the row-major output of the mask-logit GEMM): the four
 // bilinear corners of a sample point are four contiguous Q-float rows, one coalesced 128-B segment per wave.
-#include "common.h"
+#include "split_f16.h"
 #include <type_traits>
 
 namespace {
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void matcher_cost_kernel(CostParams p)
         if (nt < ntl) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int qq = wv * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int qq = mfma32_row(r, h, wv * 32);
                 p.wsA[(pc * QP + qq) * NP + nt * 32 + l32] = aA[nt][r];
                 p.wsD[(pc * QP + qq) * NP + nt * 32 + l32] = aD[nt][r];
             }
@@ -269,21 +269,9 @@ __global__ __launch_bounds__(256) void target_bits_kernel(const uint8_t *__restr
 }
 
 // N <= 32 targets: the two [Q x N] contractions on the f16 matrix cores with the split-fp16 x3 scheme of
-// gemm_bf16.hip (x = h + l*2^-11, main and cross accumulators): 12 MFMAs of 32 cycles per 32-sample batch instead of
+// split_f16.h (x = h + l*2^-11, main and cross accumulators; the fma form of the split): 12 MFMAs of 32 cycles per 32-sample batch instead of
 // 32 fp32-input MFMAs of 64 cycles, at fp32-class accuracy (~3*2^-22 relative).  |logit| < 65504 is required.
-typedef __fp16 h16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void split_pair(float a, float b, unsigned int &hi, unsigned int &lo)
-{
-    const h16x2 h = __builtin_amdgcn_cvt_pkrtz(a, b);
-    // (a - h) * 2048 == fma(h, -2048, a * 2048) exactly (a - h is exact, the factor a power of two): one multiply + one
-    // v_fma_mix_f32 (fp16 operand converted inside the fma) per value instead of convert, subtract, multiply
-    const h16x2 l = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)h[0], -2048.f, a * 2048.f), __builtin_fmaf((float)h[1], -2048.f, b * 2048.f));
-    hi = __builtin_bit_cast(unsigned int, h);
-    lo = __builtin_bit_cast(unsigned int, l);
-}
 
 // timing experiments only (scripts/build_matcher_dbg.sh): 1 no target gathers, 2 no staged-row DMA, 4 no tap-table setup, 8 no query sampling.
 // Results of such builds are wrong by construction.
@@ -464,7 +452,6 @@ __device__ __forceinline__ void matcher_cost_f16_body(const CostParams &p)
     };
     auto target_tile = [&](int tb, int buf) {
         if (tid >= 256) return;
-        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
         float val[SPT];
 #pragma unroll
         for (int j = 0; j < SPT; ++j) {
@@ -475,8 +462,8 @@ __device__ __forceinline__ void matcher_cost_f16_body(const CostParams &p)
             tsum += val[j];
         }
         unsigned int h0, l0, h1, l1;
-        split_pair(val[0], val[1], h0, l0);
-        split_pair(val[2], val[3], h1, l1);
+        split2_fma(val[0], val[1], h0, l0);
+        split2_fma(val[2], val[3], h1, l1);
         Th[buf][tn][slot * 2] = h0; Th[buf][tn][slot * 2 + 1] = h1;
         Tl[buf][tn][slot * 2] = l0; Tl[buf][tn][slot * 2 + 1] = l1;
     };
@@ -559,8 +546,8 @@ __device__ __forceinline__ void matcher_cost_f16_body(const CostParams &p)
                     sgsum += sgm;
                     xv[e] = x; sv[e] = sgm;
                 }
-                split_pair(xv[0], xv[1], xh[st][jp], xl[st][jp]);
-                split_pair(sv[0], sv[1], gh[st][jp], gl[st][jp]);
+                split2_fma(xv[0], xv[1], xh[st][jp], xl[st][jp]);
+                split2_fma(sv[0], sv[1], gh[st][jp], gl[st][jp]);
             }
             lg2sum += __builtin_amdgcn_logf(dprod);
         };
@@ -587,7 +574,6 @@ __device__ __forceinline__ void matcher_cost_f16_body(const CostParams &p)
         for (int st = 0; st < 2; ++st) {
             const f16x8 th = *reinterpret_cast<const f16x8 *>(&Th[cur][l32][8 * st + 4 * h]);
             const f16x8 tl = *reinterpret_cast<const f16x8 *>(&Tl[cur][l32][8 * st + 4 * h]);
-            typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
             const u32x4 a0 = {xh[st][0], xh[st][1], xh[st][2], xh[st][3]}, a1 = {xl[st][0], xl[st][1], xl[st][2], xl[st][3]};
             const u32x4 g0 = {gh[st][0], gh[st][1], gh[st][2], gh[st][3]}, g1 = {gl[st][0], gl[st][1], gl[st][2], gl[st][3]};
             const f16x8 xhv = __builtin_bit_cast(f16x8, a0), xlv = __builtin_bit_cast(f16x8, a1);
@@ -600,7 +586,6 @@ __device__ __forceinline__ void matcher_cost_f16_body(const CostParams &p)
             aDm = __builtin_amdgcn_mfma_f32_32x32x16_f16(ghv, th, aDm, 0, 0, 0);
         }
         } else {
-            typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
             const u32x4 a0 = {xh[0][0], xh[0][1], xh[0][2], xh[0][3]}, a1 = {xl[0][0], xl[0][1], xl[0][2], xl[0][3]};
             const u32x4 g0 = {gh[0][0], gh[0][1], gh[0][2], gh[0][3]}, g1 = {gl[0][0], gl[0][1], gl[0][2], gl[0][3]};
             const f16x8 xhv = __builtin_bit_cast(f16x8, a0), xlv = __builtin_bit_cast(f16x8, a1);
@@ -625,9 +610,9 @@ __device__ __forceinline__ void matcher_cost_f16_body(const CostParams &p)
     if (!w16) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int qq = wv * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            p.wsA[(pc * QP + qq) * NP + l32] = aAm[r] + aAx[r] * (1.0f / 2048.0f);
-            p.wsD[(pc * QP + qq) * NP + l32] = aDm[r] + aDx[r] * (1.0f / 2048.0f);
+            const int qq = mfma32_row(r, h, wv * 32);
+            p.wsA[(pc * QP + qq) * NP + l32] = join(aAm[r], aAx[r]);
+            p.wsD[(pc * QP + qq) * NP + l32] = join(aDm[r], aDx[r]);
         }
         spsum += __shfl_xor(spsum, 32, 64);
         sgsum += __shfl_xor(sgsum, 32, 64);
@@ -642,8 +627,8 @@ __device__ __forceinline__ void matcher_cost_f16_body(const CostParams &p)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int qq = (Q16 ? wv * 16 : 96) + 4 * g16 + r;
-                p.wsA[(pc * QP + qq) * NP + 16 * t + l16] = bAm[t][r] + bAx[t][r] * (1.0f / 2048.0f);
-                p.wsD[(pc * QP + qq) * NP + 16 * t + l16] = bDm[t][r] + bDx[t][r] * (1.0f / 2048.0f);
+                p.wsA[(pc * QP + qq) * NP + 16 * t + l16] = join(bAm[t][r], bAx[t][r]);
+                p.wsD[(pc * QP + qq) * NP + 16 * t + l16] = join(bDm[t][r], bDx[t][r]);
             }
         }
         spsum += __shfl_xor(spsum, 16, 64); spsum += __shfl_xor(spsum, 32, 64);
@@ -840,8 +825,6 @@ __global__ __launch_bounds__(64) void lsap_kernel(const float *__restrict__ Call
 }  // namespace
 
 extern "C" {
-
-
 
 long s2d_matcher_workspace_floats(int NL, int B, int T, int P, int H, int W)
 {
