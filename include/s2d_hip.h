@@ -657,7 +657,8 @@ int s2d_class_loss_backward_c_f32(const float *class_logits, int C1, const int *
 /* ---- keymask discovery (paths relative to /root/reference/keymask_ident) ------------------------------- */
 
 /* pred_tracks_to_binary_masks(return_mask=False), cotracker_matching.py:453-503: tracks [T][Np][2] (x,y px) ->
- * masks u8 [T][H][W] (zeroed here); torch.round (half-to-even), keep 0<=x<W, 0<=y<H. */
+ * masks u8 [T][H][W] (zeroed here); torch.round (half-to-even), keep 0<=x<W, 0<=y<H.  A point with a NaN or infinite coordinate is
+ * dropped, as torch.round(x).long() (INT64_MIN) makes the reference drop it.  H and W < 2^24, else S2D_ERR_ARG. */
 int s2d_tracks_to_masks_u8(const float *tracks, int T, int Np, int H, int W, uint8_t *masks, hipStream_t stream);
 
 /* extract_mask_matches inner loops (:665-719) for ALL frames and object ids at once: counts[t][id] =
@@ -668,9 +669,9 @@ int s2d_point_id_counts(const uint8_t *point_masks, const int64_t *idmap, int T,
                         int *counts, int *total, hipStream_t stream);
 
 /* s2d_tracks_to_masks_u8 + s2d_point_id_counts in one launch without the [T][H][W] point mask: tracks f32 [T][P][2] (x,y px) in a
- * frame of H x W, idmap int64 [T][Hi][Wi] -> the same counts int32 [T][max_id+1] and total int32 [T], bit for bit, for every finite
- * input.  One workgroup per frame: each point is rounded half to even and bounds-tested as s2d_tracks_to_masks_u8 does, points
- * with a non-finite coordinate are dropped, the frame's pixel keys are sorted in LDS and each distinct pixel is counted once
+ * frame of H x W, idmap int64 [T][Hi][Wi] -> the same counts int32 [T][max_id+1] and total int32 [T], bit for bit.
+ * One workgroup per frame: each point is rounded half to even and bounds-tested as s2d_tracks_to_masks_u8 does (points
+ * with a non-finite coordinate are dropped), the frame's pixel keys are sorted in LDS and each distinct pixel is counted once
  * (two tracks on one pixel count once, as in the scattered mask), through the nearest rule of s2d_point_id_counts.
  * Limits: P <= 32768 (the LDS sort: 4 B per key, padded to a power of two, beside 4 (max_id + 2) B of histogram within the
  * 160 KiB of one CU), max_id <= 8190, H and W < 2^24; anything else returns S2D_ERR_ARG (callers with more points use the

@@ -24,9 +24,13 @@ __global__ void scatter_tracks_kernel(const float *__restrict__ tracks, int T, i
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)T * Np) return;
     const int t = (int)(i / Np);
-    const long x = (long)rintf(tracks[2 * i]);       // torch.round: half to even, then .long()
-    const long y = (long)rintf(tracks[2 * i + 1]);
-    if (x >= 0 && x < W && y >= 0 && y < H) masks[((long)t * H + y) * W + x] = 1;
+    const float fx = tracks[2 * i], fy = tracks[2 * i + 1];
+    // torch.round(x).long() of a NaN or an infinity is INT64_MIN in the reference: the point is dropped.  The cast of such a float
+    // is undefined here (on gfx950 a NaN came out as 0 and marked row / column 0), so the test runs on the rounded floats, as in
+    // the fused kernel
+    if (!isfinite(fx) || !isfinite(fy)) return;
+    const float x = rintf(fx), y = rintf(fy);         // torch.round: half to even
+    if (x >= 0.f && x < (float)W && y >= 0.f && y < (float)H) masks[((long)t * H + (long)y) * W + (long)x] = 1;   // H, W < 2^24
 }
 
 // counts[t][id] = #{point pixels of frame t whose nearest-resized id-map value is id}; total[t] = #point pixels
@@ -81,8 +85,7 @@ __global__ __launch_bounds__(1024) void track_point_id_counts_kernel(const float
             const float fx = tr[2 * i], fy = tr[2 * i + 1];
             if (isfinite(fx) && isfinite(fy)) {
                 const float x = rintf(fx), y = rintf(fy);          // torch.round: half to even
-                // integer-valued floats against exact float bounds (W, H < 2^24): the same test as the long compare of
-                // scatter_tracks_kernel wherever that cast is defined
+                // integer-valued floats against exact float bounds (W, H < 2^24): the test of scatter_tracks_kernel
                 if (x >= 0.f && x < (float)W && y >= 0.f && y < (float)H) k = (unsigned int)y * (unsigned int)W + (unsigned int)x;
             }
         }
@@ -375,6 +378,7 @@ int s2d_color_masks_to_ids(const uint8_t *rgb, int T, int H, int W, unsigned int
 
 int s2d_tracks_to_masks_u8(const float *tracks, int T, int Np, int H, int W, uint8_t *masks, hipStream_t stream)
 {
+    if (H >= (1 << 24) || W >= (1 << 24)) return S2D_ERR_ARG;   // the kernel tests the rounded floats against (float)W, (float)H
     if (s2d_zero_async(masks, (size_t)T * H * W, stream) != S2D_OK) return S2D_ERR_LAUNCH;
     const long n = (long)T * Np;
     if (n == 0) return S2D_OK;

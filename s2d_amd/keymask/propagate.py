@@ -59,8 +59,8 @@ TRACK_COUNTS_MAX_POINTS = 32768      # s2d_track_point_id_counts' LDS sort capac
 
 def point_id_counts_from_tracks(pred_tracks, H, W, idmap: IdMap):
     """pred_tracks [1,T,P,2] or [T,P,2] (x,y) in an H x W frame -> (counts int32 [T,max_id+1], total int32 [T]) on the device:
-    pred_tracks_to_binary_masks + point_id_counts in one launch, bit for bit on finite tracks (a point with a non-finite
-    coordinate is dropped).  More points than one workgroup's LDS sort holds take the two-launch path."""
+    pred_tracks_to_binary_masks + point_id_counts in one launch, bit for bit (both drop a point with a non-finite coordinate).
+    More points than one workgroup's LDS sort holds take the two-launch path."""
     tr = pred_tracks[0] if pred_tracks.dim() == 4 else pred_tracks
     tr = tr.to(device="cuda", dtype=torch.float32).contiguous()
     T, P, _ = tr.shape
@@ -91,7 +91,7 @@ def extract_mask_matches(segm_mask_hw, pred_tracks, idmap: IdMap, v_range, match
 
 
 def extract_mask_matches_from_tracks(segm_mask_hw, pred_tracks, idmap: IdMap, v_range, matching_threshold=0.5):
-    """extract_mask_matches through the fused kernel (point_id_counts_from_tracks): the same lists for finite tracks"""
+    """extract_mask_matches through the fused kernel (point_id_counts_from_tracks): the same lists"""
     H, W = segm_mask_hw
     assert pred_tracks.shape[-3] == idmap.T
     return _matches_from_counts(*point_id_counts_from_tracks(pred_tracks, H, W, idmap), idmap, v_range, matching_threshold)

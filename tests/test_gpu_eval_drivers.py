@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.test_discovery_refs_cpu import rle_to_bbox as _rle_to_bbox
 from tests.test_eval_drivers_cpu import RESIZE_GRID, _rle_counts
 
 pytestmark = pytest.mark.gpu
@@ -53,25 +54,6 @@ def test_resize_kernel_unaligned_source_and_many_workgroups():
 
 
 # -------------------------------------------------------------------------------------------------------------- bbox kernel
-def _rle_to_bbox(counts, h, w):
-    """pycocotools rleToBbox (maskApi.c) on the run counts, in numpy-free integer steps"""
-    m = (len(counts) // 2) * 2
-    if m == 0:
-        return [0, 0, 0, 0]
-    xs, ys, xe, ye, cc, xp = w, h, 0, 0, 0, 0
-    for j in range(m):
-        cc += counts[j]
-        t = cc - j % 2
-        y = t % h
-        x = (t - y) // h
-        if j % 2 == 0:
-            xp = x
-        elif xp < x:
-            ys, ye = 0, h - 1
-        xs, xe, ys, ye = min(xs, x), max(xe, x), min(ys, y), max(ye, y)
-    return [xs, ys, xe - xs + 1, ye - ys + 1]
-
-
 def test_plane_bbox_kernel_matches_rle_to_bbox():
     from s2d_amd import ops
     from s2d_amd.ytvis_eval import plane_areas, plane_bboxes
