@@ -709,6 +709,24 @@ int s2d_visibility_curve_f32(const uint8_t *visibility, int T, int Np, float *cu
 int s2d_local_corr_f32(const float *fmap_nhwc, const float *coords, const float *support, int T, int Np, int H, int W, int C,
                        int r, float *corr, hipStream_t stream);
 
+/* Built-in baseline point tracker of keymask discovery (s2d_amd/keymask/block_tracker.py; self-defined -- the reference tracks with
+ * CoTracker, third party): integer block matching on grey frames.  Both calls have exactly one correct output.
+ * s2d_video_grey_u8: video f32 [T][3][H][W] (RGB, nominally 0..255) -> grey u8 [T][H][W]; per channel
+ * c = (int)rintf(fminf(fmaxf(v, 0), 255)) (half to even; NaN -> 0; +-inf clamp), grey = (77 r + 150 g + 29 b + 128) >> 8. */
+int s2d_video_grey_u8(const float *video, int T, int H, int W, uint8_t *grey, hipStream_t stream);
+
+/* points int32 [N][2] = (x, y) inside the frame (DEVICE; a point outside is clamped into it), q the query frame -> tracks f32
+ * [T][N][2] (integer-valued x, y), vis u8 [T][N] (0 / 1).  All coordinates clamp to the frame (border replicate).  Template of
+ * point p: Tm[j][i] = grey[q][p.y + j][p.x + i], |i|, |j| <= R, never updated.  Frame q: track = p, visible.  Forward: c = p; for
+ * t = q+1 .. T-1 the candidates are the (dx, dy), |dx|, |dy| <= S, whose centre c + (dx, dy) lies inside the frame, a candidate's
+ * cost is sum |Tm[j][i] - grey[t][c.y + dy + j][c.x + dx + i]|, the best one is the minimum of (cost, dx^2 + dy^2, dy, dx) taken
+ * lexicographically, and the point is visible iff cost <= tau (2R+1)^2; visible: c += (dx, dy); not visible: c stays, so a lost
+ * point keeps searching round its last good position; tracks[t] = c, vis[t] = visible.  backward != 0: the same from c = p for
+ * t = q-1 .. 0; otherwise frames t < q hold p with vis = 0.  One wave per (point, direction); no input makes the kernel read
+ * outside grey.  1 <= R <= 7, 1 <= S <= 24, 0 <= tau <= 255, 0 <= q < T, H and W < 2^15; anything else returns S2D_ERR_ARG. */
+int s2d_block_track_u8(const uint8_t *grey, int T, int H, int W, const int *points, int N, int q, int backward, int R, int S,
+                       int tau, float *tracks, uint8_t *vis, hipStream_t stream);
+
 /* ---- timing helpers for the benchmark's per-launch roofline (not on the data path) ------------------------ */
 
 /* HIP events created with hipEventDisableSystemFence (handles are opaque integers, 0 = failure). */

@@ -1,0 +1,170 @@
+// Block-matching point tracker for keymask discovery (s2d_amd/keymask/block_tracker.py): integer SAD search on u8 grey frames.
+// Self-defined (the reference's tracker is CoTracker, third party): a baseline, not a restatement.  Every output is an integer
+// decision, so tests/block_tracker_ref.py reproduces both kernels bit for bit.
+//
+//  grey pass   video f32 [T][3][H][W] (RGB, nominally 0..255) -> u8 [T][H][W]: per channel round-half-even of the value clamped
+//              to [0, 255] (NaN -> 0), then (77 r + 150 g + 29 b + 128) >> 8
+//  tracker     one wave per (point, direction).  Template = the (2R+1)^2 patch round the point in the query frame, never
+//              updated.  Per frame the wave stages the (2(R+S)+1)^2 region round its current centre into LDS (border
+//              replicate), its lanes take the (2S+1)^2 displacements in rounds of 64, and the minimum of
+//              (cost, dx^2+dy^2, dy, dx) is reduced as one packed 64-bit key.  cost <= tau (2R+1)^2: visible, the centre moves;
+//              otherwise the centre stays and the point keeps searching round its last good position.
+//
+// LDS image: region rows of `pitch` dwords (odd: consecutive rows start on different banks), the row's bytes packed 4 per dword;
+// a patch row that starts at byte b is read as K + 1 aligned dwords from b >> 2 and shifted into place (v_alignbyte_b32), then
+// v_sad_u8 against the template dword.  The template's pad bytes are zero and the same mask clears the region's.
+#include "common.h"
+
+namespace {
+
+constexpr int BT_MAX_R = 7, BT_MAX_S = 24;
+constexpr int BT_MAX_ROWS = 2 * (BT_MAX_R + BT_MAX_S) + 1;                    // 63
+constexpr int BT_MAX_PITCH = ((2 * BT_MAX_S) >> 2) + 4 + 1;                    // 17 dwords: first dword of the last patch + K + 1
+
+__global__ __launch_bounds__(256) void video_grey_kernel(const float *__restrict__ video, long HW, long n, uint8_t *__restrict__ grey)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long t = i / HW, p = i - t * HW;
+    const float *src = video + t * 3 * HW + p;
+    int c[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = (int)rintf(fminf(fmaxf(src[k * HW], 0.f), 255.f));   // fmaxf(NaN, 0) = 0
+    grey[i] = (uint8_t)((77 * c[0] + 150 * c[1] + 29 * c[2] + 128) >> 8);
+}
+
+__device__ __forceinline__ int clampi(int v, int hi) { return min(max(v, 0), hi); }
+
+// 4 bytes of row `row` from column x0 on, columns clamped to the frame
+__device__ __forceinline__ unsigned int load4_clamped(const uint8_t *__restrict__ row, int x0, int W)
+{
+    unsigned int w = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) w |= (unsigned int)row[clampi(x0 + b, W - 1)] << (8 * b);
+    return w;
+}
+
+// K = dwords per patch row = ceil((2R+1) / 4)
+template <int K>
+__global__ __launch_bounds__(64) void block_track_kernel(const uint8_t *__restrict__ grey, int T, int H, int W,
+                                                         const int *__restrict__ points, int N, int q, int R, int S, int tau,
+                                                         float *__restrict__ tracks, uint8_t *__restrict__ vis)
+{
+    __shared__ unsigned int region[BT_MAX_ROWS * BT_MAX_PITCH];
+    __shared__ unsigned int tmpl[(2 * BT_MAX_R + 1) * 4];
+    const int n = blockIdx.x, backward = blockIdx.y, lane = threadIdx.x;
+    const int P = 2 * R + 1, D = 2 * (R + S) + 1, C = 2 * S + 1;
+    const int pitch = (((2 * S) >> 2) + K + 1) | 1;
+    const long HW = (long)H * W;
+    // a point outside the frame (outside the contract) is clamped into it: the centre then always has a valid candidate
+    const int px = clampi(points[2 * n], W - 1), py = clampi(points[2 * n + 1], H - 1);
+    const unsigned int lastmask = 0xFFFFFFFFu >> (8 * (4 * K - P));
+
+    if (lane < P * 4) {
+        const int j = lane >> 2, k = lane & 3;
+        unsigned int w = 0;
+        if (k < K) {
+            w = load4_clamped(grey + (long)q * HW + (long)clampi(py - R + j, H - 1) * W, px - R + 4 * k, W);
+            if (k == K - 1) w &= lastmask;
+        }
+        tmpl[lane] = w;
+    }
+    if (!backward && lane == 0) {
+        // the query frame; without a backward wave (gridDim.y == 1) the frames before it hold the point, invisible
+        for (int t = gridDim.y == 1 ? 0 : q; t <= q; ++t) {
+            tracks[((long)t * N + n) * 2] = (float)px;
+            tracks[((long)t * N + n) * 2 + 1] = (float)py;
+            vis[(long)t * N + n] = t == q;
+        }
+    }
+    int cx = px, cy = py;
+    const int step = backward ? -1 : 1;
+    const unsigned int limit = (unsigned int)(tau * P * P);
+    for (int t = q + step; t >= 0 && t < T; t += step) {
+        __syncthreads();                                    // the template stores / the previous frame's reads are done
+        const uint8_t *fr = grey + (long)t * HW;
+        const int ox = cx - S - R, oy = cy - S - R;
+        for (int e = lane; e < D * pitch; e += 64) {
+            const int ry = e / pitch, wx = e - ry * pitch;
+            region[e] = load4_clamped(fr + (long)clampi(oy + ry, H - 1) * W, ox + 4 * wx, W);
+        }
+        __syncthreads();
+        unsigned long long best = ~0ull;
+        for (int cand = lane; cand < C * C; cand += 64) {
+            const int dyi = cand / C, dxi = cand - dyi * C;
+            const int nx = cx + dxi - S, ny = cy + dyi - S;
+            if (nx < 0 || nx >= W || ny < 0 || ny >= H) continue;
+            const unsigned int *row = region + dyi * pitch + (dxi >> 2);
+            const unsigned int sh = dxi & 3;
+            unsigned int cost = 0;
+            for (int j = 0; j < P; ++j, row += pitch) {
+                unsigned int lo = row[0];
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const unsigned int hi = row[k + 1];
+                    unsigned int v = __builtin_amdgcn_alignbyte(hi, lo, sh);
+                    if (k == K - 1) v &= lastmask;
+                    cost = __builtin_amdgcn_sad_u8(v, tmpl[j * 4 + k], cost);
+                    lo = hi;
+                }
+            }
+            const int dx = dxi - S, dy = dyi - S;
+            // cost < 2^16, d^2 < 2^11, dy + S and dx + S < 2^6 each
+            const unsigned long long key = ((unsigned long long)cost << 23) | ((unsigned long long)(dx * dx + dy * dy) << 12) |
+                                           ((unsigned long long)dyi << 6) | (unsigned long long)dxi;
+            best = key < best ? key : best;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long other = __shfl_xor(best, o, 64);
+            best = other < best ? other : best;
+        }
+        const bool visible = (unsigned int)(best >> 23) <= limit;
+        if (visible) {
+            cx += (int)(best & 63) - S;
+            cy += (int)((best >> 6) & 63) - S;
+        }
+        if (lane == 0) {
+            tracks[((long)t * N + n) * 2] = (float)cx;
+            tracks[((long)t * N + n) * 2 + 1] = (float)cy;
+            vis[(long)t * N + n] = visible;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int s2d_video_grey_u8(const float *video, int T, int H, int W, uint8_t *grey, hipStream_t stream)
+{
+    if (T < 0 || H < 1 || W < 1) return S2D_ERR_ARG;
+    const long HW = (long)H * W, n = (long)T * HW;
+    if (n == 0) return S2D_OK;
+    if (n > 256L * 0x7FFFFFFF) return S2D_ERR_ARG;
+    hipLaunchKernelGGL(video_grey_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, video, HW, n, grey);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_block_track_u8(const uint8_t *grey, int T, int H, int W, const int *points, int N, int q, int backward, int R, int S,
+                       int tau, float *tracks, uint8_t *vis, hipStream_t stream)
+{
+    if (R < 1 || R > BT_MAX_R || S < 1 || S > BT_MAX_S || tau < 0 || tau > 255) return S2D_ERR_ARG;
+    if (T < 1 || q < 0 || q >= T || N < 0 || H < 1 || W < 1 || H >= (1 << 15) || W >= (1 << 15)) return S2D_ERR_ARG;
+    if (N == 0) return S2D_OK;
+    const dim3 grid(N, backward && q > 0 ? 2 : 1);
+#define S2D_BT(k)                                                                                                               \
+    case k:                                                                                                                     \
+        hipLaunchKernelGGL(block_track_kernel<k>, grid, dim3(64), 0, stream, grey, T, H, W, points, N, q, R, S, tau, tracks, vis); \
+        break;
+    switch ((2 * R + 1 + 3) / 4) {
+        S2D_BT(1) S2D_BT(2) S2D_BT(3) S2D_BT(4)
+    default: return S2D_ERR_ARG;
+    }
+#undef S2D_BT
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+}  // extern "C"

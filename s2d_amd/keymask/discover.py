@@ -2,7 +2,7 @@
 
     python -m s2d_amd.keymask.discover --video-base-path D/DAVIS/JPEGImages/480p --mask-base-path M --save-path S \\
         --visibility-maps-output-base V --visibility-clusters-output-base C --annotation-output-path A \\
-        --tracker cotracker --tracker-checkpoint scaled_offline.pth
+        --tracker cotracker --tracker-checkpoint scaled_offline.pth          (or --tracker block: the built-in baseline)
 
 Restates keymask_ident/main_keymask_ident.py and its per-video stages with their file names, layouts, JSON contents and
 observable quirks:
@@ -73,7 +73,8 @@ def parse_args(argv=None):
     p.add_argument("--job-id", default=0, type=int, help="Job ID for distributed training")
     p.add_argument("--videos-per-job", default=-1, type=int, help="Number of videos to process per job")
     p.add_argument("--debug", default=False, action="store_true", help="Debug mode")
-    p.add_argument("--tracker", default="cotracker", help="'cotracker' or 'pkg.module:factory'")
+    p.add_argument("--tracker", default="cotracker",
+                   help="'cotracker', 'block' (the built-in block-matching baseline: no package, no weights) or 'pkg.module:factory'")
     p.add_argument("--tracker-checkpoint", default=None, help="passed to the tracker (CoTracker: scaled_offline.pth)")
     p.add_argument("--dataset-name", default=None, help="dataset name instead of the one detected in --video-base-path")
     return p.parse_args(argv)

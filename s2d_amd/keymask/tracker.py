@@ -8,8 +8,9 @@ video float [1,T,3,H,W] (RGB, 0..255) on the device, segm_mask uint8 [1,1,H,W] w
 pred_tracks [1,T,N,2] (x, y) pixels and pred_visibility [1,T,N] bool.
 
 `load_tracker("cotracker", checkpoint)` builds CoTracker's offline predictor as the reference does (:318-328).  CoTracker is
-third party and optional: it is imported only there.  `load_tracker("pkg.module:attr")` imports a factory and calls it
-(with `checkpoint=` when one is given); that is how tests and other trackers plug in."""
+third party and optional: it is imported only there.  `load_tracker("block")` returns the built-in block-matching baseline
+(block_tracker.BlockTracker: no package, no weights; its limits are stated there).  `load_tracker("pkg.module:attr")` imports a
+factory and calls it (with `checkpoint=` when one is given); that is how tests and other trackers plug in."""
 import importlib
 
 
@@ -25,8 +26,11 @@ def load_tracker(spec, checkpoint=None):
         model = CoTrackerPredictor(checkpoint=checkpoint)
         import torch
         return model.cuda() if torch.cuda.is_available() else model
+    if spec == "block":
+        from .block_tracker import BlockTracker
+        return BlockTracker()
     mod, sep, attr = spec.partition(":")
     if not sep or not mod or not attr:
-        raise ValueError(f"tracker spec {spec!r}: expected 'cotracker' or 'pkg.module:attr'")
+        raise ValueError(f"tracker spec {spec!r}: expected 'cotracker', 'block' or 'pkg.module:attr'")
     factory = getattr(importlib.import_module(mod), attr)
     return factory(checkpoint=checkpoint) if checkpoint is not None else factory()

@@ -1,0 +1,253 @@
+"""GPU checks of the built-in block tracker (csrc/block_track.hip, s2d_amd/keymask/block_tracker.py).  Both kernels make integer
+decisions only, so every comparison with the numpy restatement (tests/block_tracker_ref.py) is an equality; together with
+tests/test_block_tracker_refs_cpu.py the device therefore equals the ground truth wherever that is guaranteed.  The last test runs
+discovery end to end with `--tracker block` on the textured scenes and records (does not assert) how its groups compare with a
+ground-truth tracker's."""
+import glob
+import json
+import os
+import random
+
+import numpy as np
+import pytest
+import torch
+
+from tests import block_tracker_ref as B
+from tests.golden import keymask_stub_tracker as S
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _grey_dev(video):
+    from s2d_amd._lib import lib
+    v = torch.from_numpy(video).cuda()
+    T, _, H, W = v.shape
+    out = torch.empty((T, H, W), device="cuda", dtype=torch.uint8)
+    lib().call("s2d_video_grey_u8", v, T, H, W, out, _stream())
+    return out
+
+
+def _track_dev(grey, points, q, backward, R, S_, tau):
+    from s2d_amd._lib import lib
+    g = torch.from_numpy(np.ascontiguousarray(grey)).cuda()
+    T, H, W = g.shape
+    pts = torch.from_numpy(np.ascontiguousarray(points, dtype=np.int32)).cuda()
+    N = pts.shape[0]
+    tracks = torch.full((T, N, 2), float("nan"), device="cuda")
+    vis = torch.full((T, N), 7, device="cuda", dtype=torch.uint8)            # every element has to be written
+    lib().call("s2d_block_track_u8", g, T, H, W, pts, N, q, int(backward), R, S_, tau, tracks, vis, _stream())
+    return tracks.cpu().numpy(), vis.cpu().numpy()
+
+
+def test_grey_pass_equals_the_reference():
+    rng = np.random.default_rng(1)
+    T, H, W = 2, 5, 7
+    v = (rng.random((T, 3, H, W)) * 270 - 8).astype(np.float32)
+    special = np.array([0.5, 1.5, 2.5, 254.5, -3, 300, np.nan, np.inf, -np.inf], np.float32)
+    flat = v.reshape(-1)
+    flat[rng.choice(flat.size, 3 * len(special), replace=False)] = np.tile(special, 3)
+    v[0, :, 0, 0] = (0.5, 1.5, 2.5)
+    v[1, :, 4, 6] = (254.5, np.nan, np.inf)
+    got = _grey_dev(v).cpu().numpy()
+    assert got.dtype == np.uint8 and np.array_equal(got, B.grey_ref(v))
+
+
+def _small_scene():
+    """u8 [6,37,53]: a textured background with two textured patches that move, one of them out of the frame"""
+    rng = np.random.default_rng(7)
+    T, H, W = 6, 37, 53
+    bg = B._texture(rng, H, W)[..., 0]
+    a, b = B._texture(rng, 14, 16)[..., 0], B._texture(rng, 12, 12)[..., 0]
+    out = np.empty((T, H, W), np.uint8)
+    for t in range(T):
+        f = bg.copy()
+        y, x = 4 + t, 6 + 5 * t                                              # (1, 5) per frame
+        f[y:y + 14, x:x + 16] = a
+        y, x = 22 - 2 * t, 38 + 3 * t                                        # (-2, 3) per frame, leaves on the right
+        f[y:y + 12, x:min(x + 12, W)] = b[:, :max(min(12, W - x), 0)]
+        out[t] = f
+    return out
+
+
+def _small_points(H, W):
+    g = B.grid_ref(8, H, W)
+    corners = [(0, 0), (W - 1, 0), (0, H - 1), (W - 1, H - 1)]
+    border = [(W // 2, 0), (W // 3, H - 1), (0, H // 2), (W - 1, H // 3), (1, 1), (W - 2, H - 2)]
+    return np.concatenate([g, np.array(corners + border)]).astype(np.int32)
+
+
+@pytest.mark.parametrize("params", [(5, 16, 12), (3, 4, 0), (7, 24, 255), (1, 1, 12)])
+def test_small_frame_equals_the_reference(params):
+    R, S_, tau = params
+    grey = _small_scene()
+    T, H, W = grey.shape
+    pts = _small_points(H, W)
+    moved = 0
+    for q, back in ((2, True), (0, False), (T - 1, True), (3, False)):
+        want_t, want_v = B.block_track_ref(grey, pts, q, back, R, S_, tau)
+        got_t, got_v = _track_dev(grey, pts, q, back, R, S_, tau)
+        assert np.array_equal(got_v, want_v), (q, back)
+        assert np.array_equal(got_t, want_t), (q, back)
+        moved += int((want_t != pts[None].astype(np.float32)).any(-1).sum())
+    assert moved > 0 or S_ < 4                              # 5 px per frame is beyond a search radius of 1
+
+
+def test_tie_rule():
+    T, H, W, R, S_ = 4, 48, 64, 3, 6
+    yy, xx = np.mgrid[0:H, 0:W]
+    pts = np.concatenate([B.grid_ref(6, H, W), np.array([(0, 0), (W - 1, H - 1)])]).astype(np.int32)
+    m = R + S_ + 2 * T                                  # a point drifts by 2 px per frame at the most
+    interior = (pts[:, 0] >= m) & (pts[:, 0] < W - m) & (pts[:, 1] >= m) & (pts[:, 1] < H - m)
+    assert interior.sum() >= 4
+    base = pts[None].astype(np.float32)
+
+    def run(frames, q=0, back=False):
+        got = _track_dev(frames, pts, q, back, R, S_, 12)
+        want = B.block_track_ref(frames, pts, q, back, R, S_, 12)
+        assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+        return got
+
+    # constant frames: every candidate costs 0, d^2 = 0 wins
+    tr, vis = run(np.full((T, H, W), 93, np.uint8), q=1, back=True)
+    assert np.array_equal(tr, np.broadcast_to(base, tr.shape)) and vis.all()
+    # period-4 vertical stripes shifted by 4 px per frame: zero cost at dx = 0, +-4 and every dy; the point stays
+    stripes = lambda shift_x, shift_y: np.stack([(((xx - shift_x * t) % 4 < 2) * 200 + ((yy - shift_y * t) % 4 < 2) * 40 * (shift_y != 0))
+                                                 .astype(np.uint8) for t in range(T)])
+    tr, vis = run(stripes(4, 0))
+    assert np.array_equal(tr[:, interior], np.broadcast_to(base, tr.shape)[:, interior]) and vis[:, interior].all()
+    # shifted by 2 px: zero cost at dx = -2 and dx = +2 (d^2 = 4 both, dy = 0 both): the smaller dx wins
+    tr, vis = run(stripes(2, 0))
+    for t in range(T):
+        assert np.array_equal(tr[t, interior], (pts[interior] + (-2 * t, 0)).astype(np.float32)) and vis[t, interior].all()
+    # a period-4 pattern in both axes shifted by (2, 2): (+-2, +-2) all cost 0 with d^2 = 8: the smaller dy, then the smaller dx
+    tr, vis = run(stripes(2, 2))
+    for t in range(T):
+        assert np.array_equal(tr[t, interior], (pts[interior] + (-2 * t, -2 * t)).astype(np.float32)) and vis[t, interior].all()
+
+
+@pytest.fixture(scope="module")
+def videos():
+    return {name: torch.from_numpy(B.video_f32(name)).cuda()[None] for name in S.SCENES}
+
+
+def test_textured_scene_calls_equal_the_reference(videos):
+    from s2d_amd.keymask.block_tracker import BlockTracker
+    tracker = BlockTracker()
+    for name, q, obj in B.CALLS:
+        pts, want_t, want_v = B.reference_call(name, q, obj)
+        mask = torch.from_numpy(B.call_mask(name, q, obj))[None, None]
+        tracks, vis = tracker(videos[name], grid_size=50, grid_query_frame=q, segm_mask=mask, backward_tracking=q > 0)
+        assert tracks.shape == (1, want_t.shape[0], len(pts), 2) and tracks.dtype == torch.float32 and tracks.is_cuda
+        assert vis.shape == tracks.shape[:3] and vis.dtype == torch.bool
+        assert np.array_equal(vis[0].cpu().numpy(), want_v.astype(bool)), (name, q, obj)
+        assert np.array_equal(tracks[0].cpu().numpy(), want_t), (name, q, obj)
+
+
+def test_empty_mask_grey_cache_and_in_place_edit(videos):
+    from s2d_amd.keymask.block_tracker import BlockTracker
+    tracker = BlockTracker()
+    video = videos["vid_a"].clone()
+    T, H, W = video.shape[1], video.shape[-2], video.shape[-1]
+    tracks, vis = tracker(video, grid_size=50, grid_query_frame=0, segm_mask=torch.zeros((1, 1, H, W), dtype=torch.uint8))
+    assert tracks.shape == (1, T, 0, 2) and vis.shape == (1, T, 0) and vis.dtype == torch.bool
+    assert tracker._grey is None                                               # nothing was launched, not even the grey pass
+    mask = torch.from_numpy(B.call_mask("vid_a", 0, 2))[None, None]
+    pts, want_t, want_v = B.reference_call("vid_a", 0, 2)
+    t1, v1 = tracker(video, grid_size=50, grid_query_frame=0, segm_mask=mask)
+    grey = tracker._grey
+    t2, v2 = tracker(video, grid_size=50, grid_query_frame=0, segm_mask=mask)
+    assert tracker._grey is grey                                               # the second call took the cached frames
+    assert torch.equal(t1, t2) and torch.equal(v1, v2) and np.array_equal(t1[0].cpu().numpy(), want_t)
+    # an in-place edit: the frames after the query frame become copies of it, so nothing moves any more
+    video[:, 1:] = video[:, :1]
+    t3, v3 = tracker(video, grid_size=50, grid_query_frame=0, segm_mask=mask)
+    assert tracker._grey is not grey
+    assert np.array_equal(t3[0].cpu().numpy(), np.broadcast_to(pts.astype(np.float32), want_t.shape)) and bool(v3.all())
+    assert not np.array_equal(want_t, np.broadcast_to(pts.astype(np.float32), want_t.shape))
+
+
+@pytest.mark.parametrize("bad", [dict(R=8), dict(S_=25), dict(q=6), dict(R=0), dict(S_=0), dict(tau=256), dict(tau=-1), dict(q=-1)])
+def test_export_refuses(bad):
+    grey = _small_scene()
+    kw = dict(q=0, backward=False, R=5, S_=16, tau=12)
+    kw.update(bad)
+    with pytest.raises(RuntimeError):
+        _track_dev(grey, _small_points(*grey.shape[1:]), **kw)
+
+
+# ------------------------------------------------------------------------------------------------------------------ end to end
+def _discover(work, tracker=None, extra=()):
+    from s2d_amd.keymask.discover import parse_args, run
+    cwd = os.getcwd()
+    os.chdir(work)                  # relative paths: the stages derive a split from substrings such as "test" of the video path
+    try:
+        args = parse_args(["--video-base-path", S.FRAMES_DIR, "--mask-base-path", S.MASKS_DIR, "--save-path", "seg_masks",
+                           "--visibility-maps-output-base", "vis_maps", "--visibility-clusters-output-base", "vis_clusters",
+                           "--annotation-output-path", "annotations", *extra])
+        return run(args, tracker=tracker)
+    finally:
+        os.chdir(cwd)
+
+
+def _stage1(work, name):
+    path, = glob.glob(os.path.join(work, "vis_maps", "DAVIS", "*", "data", name + ".json"))
+    doc = json.load(open(path))["video_data"]
+    rows = [(f["frame_id"], o["object_id"]) for f in doc for o in f["data"]]
+    curves = np.array([o["visibility"] for f in doc for o in f["data"]], np.float64)
+    return rows, curves
+
+
+def _figures(work):
+    out = {}
+    for name in sorted(S.SCENES):
+        ann = json.load(open(os.path.join(work, "annotations", name + ".json")))["annotations"]
+        out[name] = {"annotations": len(ann),
+                     "frames_covered": [sum(s is not None for s in a["segmentations"]) for a in ann]}
+    return out
+
+
+def test_discovery_end_to_end_with_the_block_tracker(tmp_path):
+    from s2d_amd.config import load_config
+    from s2d_amd.data.train_loader import ClipSettings, load_ytvis_train, map_clip
+    from s2d_amd.keymask.formats import merge_ytvis_jsons
+    works = {}
+    for kind in ("block", "truth"):
+        works[kind] = str(tmp_path / kind)
+        os.makedirs(works[kind])
+        B.write_textured_dataset(works[kind])
+    report = _discover(works["block"], extra=["--tracker", "block"])
+    assert (report["videos"], report["done"], report["failed"]) == (2, 2, 0)
+    truth_report = _discover(works["truth"], tracker=B.TruthTracker())
+    assert (truth_report["done"], truth_report["failed"]) == (2, 0)
+    figures = {"block": _figures(works["block"]), "truth": _figures(works["truth"]), "stage1_binarised_at_0.3": {}}
+    for name in sorted(S.SCENES):
+        rows, curves = _stage1(works["block"], name)
+        rows_t, curves_t = _stage1(works["truth"], name)
+        assert rows == rows_t
+        diff = int(((curves > 0.3) != (curves_t > 0.3)).sum())
+        figures["stage1_binarised_at_0.3"][name] = {"entries": int(curves.size), "differ_from_truth": diff}
+        assert figures["block"][name]["annotations"] >= 1
+    print(json.dumps(figures))
+    out = os.environ.get("S2D_BLOCK_TRACKER_FIGURES")                          # a measurement: recorded, not asserted
+    if out:
+        with open(out, "w") as f:
+            json.dump(figures, f, indent=1)
+    # the output feeds the merge step and the training loader, as the stub-tracker driver test does
+    merged = os.path.join(works["block"], "merged", "train.json")
+    os.makedirs(os.path.dirname(merged))
+    doc = merge_ytvis_jsons(os.path.join(works["block"], "annotations"), merged, -1.0)
+    assert [v["id"] for v in doc["videos"]] == [1, 2] and len(doc["annotations"]) >= 2
+    recs = load_ytvis_train(merged, os.path.join(works["block"], S.FRAMES_DIR))
+    assert len(recs) == 2
+    st = ClipSettings(load_config(os.path.join(GOLDEN, "kd_config.json"), ["INPUT.MIN_SIZE_TRAIN", "(64,)", "INPUT.CROP.ENABLED", "False"]))
+    for k, rec in enumerate(recs):
+        clip = map_clip(rec, random.Random(k), np.random.RandomState(k), st, device="cuda:0")
+        assert len(clip["image"]) == st.num_frames
+        assert sum(int(i["gt_masks"].shape[0]) for i in clip["instances"]) > 0
