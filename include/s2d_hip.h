@@ -727,6 +727,22 @@ int s2d_video_grey_u8(const float *video, int T, int H, int W, uint8_t *grey, hi
 int s2d_block_track_u8(const uint8_t *grey, int T, int H, int W, const int *points, int N, int q, int backward, int R, int S,
                        int tau, float *tracks, uint8_t *vis, hipStream_t stream);
 
+/* The same tracker with a wider search and a live template (keymask/block_tracker.py LiveBlockTracker, --tracker block-live).
+ * Inputs, outputs, clamping of points and border replicate as in s2d_block_track_u8.  Every (point, direction) -- forward, and
+ * backward when backward != 0 -- carries its own template L, |i|, |j| <= R, which starts as the query-frame patch
+ * L[j][i] = grey[q][p.y + j][p.x + i]; the two directions never share one.  Frame q: track = p, visible.  Forward: c = p; for
+ * t = q+1 .. T-1 the candidates are the (dx, dy), |dx|, |dy| <= S, whose centre c + (dx, dy) lies inside the frame, a candidate's
+ * cost is sum |L[j][i] - grey[t][c.y + dy + j][c.x + dx + i]| against the CURRENT L, the best one is the minimum of
+ * (cost, dx^2 + dy^2, dy, dx) taken lexicographically, and the point is visible iff cost <= tau (2R+1)^2; visible: c += (dx, dy);
+ * not visible: c stays and the point keeps searching round its last good position; tracks[t] = c, vis[t] = visible.  Then, if
+ * the point is visible and cost <= tau_u (2R+1)^2, L[j][i] = grey[t][c.y + j][c.x + i] round the new c (border replicate);
+ * otherwise L is kept.  tau_u = -1 never refreshes, tau_u = tau refreshes at every visible frame.  backward != 0: the same from
+ * c = p and the query-frame patch for t = q-1 .. 0; otherwise frames t < q hold p with vis = 0.  With tau_u = -1 and S <= 24 the
+ * output equals s2d_block_track_u8's bit for bit.  One wave per (point, direction); no input makes the kernel read outside grey.
+ * 1 <= R <= 7, 1 <= S <= 64, 0 <= tau <= 255, -1 <= tau_u <= tau, 0 <= q < T, H and W < 2^15; anything else returns S2D_ERR_ARG. */
+int s2d_block_track_live_u8(const uint8_t *grey, int T, int H, int W, const int *points, int N, int q, int backward, int R, int S,
+                            int tau, int tau_u, float *tracks, uint8_t *vis, hipStream_t stream);
+
 /* ---- timing helpers for the benchmark's per-launch roofline (not on the data path) ------------------------ */
 
 /* HIP events created with hipEventDisableSystemFence (handles are opaque integers, 0 = failure). */

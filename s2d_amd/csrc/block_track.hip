@@ -1,6 +1,6 @@
 // Block-matching point tracker for keymask discovery (s2d_amd/keymask/block_tracker.py): integer SAD search on u8 grey frames.
 // Self-defined (the reference's tracker is CoTracker, third party): a baseline, not a restatement.  Every output is an integer
-// decision, so tests/block_tracker_ref.py reproduces both kernels bit for bit.
+// decision, so tests/block_tracker_ref.py and tests/live_tracker_ref.py reproduce the kernels bit for bit.
 //
 //  grey pass   video f32 [T][3][H][W] (RGB, nominally 0..255) -> u8 [T][H][W]: per channel round-half-even of the value clamped
 //              to [0, 255] (NaN -> 0), then (77 r + 150 g + 29 b + 128) >> 8
@@ -9,6 +9,8 @@
 //              replicate), its lanes take the (2S+1)^2 displacements in rounds of 64, and the minimum of
 //              (cost, dx^2+dy^2, dy, dx) is reduced as one packed 64-bit key.  cost <= tau (2R+1)^2: visible, the centre moves;
 //              otherwise the centre stays and the point keeps searching round its last good position.
+//  live        the tracker with S up to 64 and a template that is rewritten from the frame where the match is good enough
+//              (s2d_block_track_live_u8; described in front of its kernel below)
 //
 // LDS image: region rows of `pitch` dwords (odd: consecutive rows start on different banks), the row's bytes packed 4 per dword;
 // a patch row that starts at byte b is read as K + 1 aligned dwords from b >> 2 and shifted into place (v_alignbyte_b32), then
@@ -132,6 +134,121 @@ __global__ __launch_bounds__(64) void block_track_kernel(const uint8_t *__restri
     }
 }
 
+// ---- the wide-search tracker with a live template (s2d_block_track_live_u8) -------------------------------------------------
+// The same wave-per-(point, direction) search, with S up to 64 and a template that follows the point: after the decision of frame
+// t a visible point whose cost is at most tau_u (2R+1)^2 takes the patch round its new centre as its template.  The new patch
+// lies inside the staged region (|dx|, |dy| <= S), whose bytes already are the border-replicated frame, so it is copied from LDS
+// with the aligned read of the cost loop.  The region is dynamic LDS, D rows of `pitch` dwords (at R = 7, S = 64: 143 x 37
+// dwords, 21 KB), so a small S keeps the occupancy of the fixed-template kernel.
+//
+// Key: cost < 2^16 (255 * 15^2), d^2 <= 2 * 64^2 < 2^14, dy + S and dx + S <= 128 < 2^8 each: 16 + 14 + 8 + 8 = 46 bits.
+//
+// Pruning (exact): a candidate whose partial cost exceeds tau (2R+1)^2 can only be the minimum when every candidate exceeds it,
+// and then the point is invisible, stays where it is and keeps its template -- the minimum itself is never looked at; a
+// candidate whose partial cost exceeds the lane's best cost so far cannot be the lane's minimum.  Rows only add to the cost, so
+// the row loop stops at either bound.
+constexpr int BTL_MAX_S = 64;
+
+template <int K>
+__global__ __launch_bounds__(64) void block_track_live_kernel(const uint8_t *__restrict__ grey, int T, int H, int W,
+                                                              const int *__restrict__ points, int N, int q, int R, int S, int tau,
+                                                              int tau_u, float *__restrict__ tracks, uint8_t *__restrict__ vis)
+{
+    extern __shared__ unsigned int live_region[];
+    __shared__ unsigned int tmpl[(2 * BT_MAX_R + 1) * 4];
+    const int n = blockIdx.x, backward = blockIdx.y, lane = threadIdx.x;
+    const int P = 2 * R + 1, D = 2 * (R + S) + 1, C = 2 * S + 1;
+    const int pitch = (((2 * S) >> 2) + K + 1) | 1;
+    const long HW = (long)H * W;
+    const int px = clampi(points[2 * n], W - 1), py = clampi(points[2 * n + 1], H - 1);
+    const unsigned int lastmask = 0xFFFFFFFFu >> (8 * (4 * K - P));
+    const int tj = lane >> 2, tk = lane & 3;                  // the template dword of this lane (lanes below 4 P)
+
+    if (lane < P * 4) {
+        unsigned int w = 0;
+        if (tk < K) {
+            w = load4_clamped(grey + (long)q * HW + (long)clampi(py - R + tj, H - 1) * W, px - R + 4 * tk, W);
+            if (tk == K - 1) w &= lastmask;
+        }
+        tmpl[lane] = w;                                       // dwords K .. 3 of a row stay zero for good
+    }
+    if (!backward && lane == 0) {
+        for (int t = gridDim.y == 1 ? 0 : q; t <= q; ++t) {
+            tracks[((long)t * N + n) * 2] = (float)px;
+            tracks[((long)t * N + n) * 2 + 1] = (float)py;
+            vis[(long)t * N + n] = t == q;
+        }
+    }
+    int cx = px, cy = py;
+    const int step = backward ? -1 : 1;
+    const unsigned int limit = (unsigned int)(tau * P * P);
+    const int limit_u = tau_u * P * P;                        // negative: never refreshed
+    for (int t = q + step; t >= 0 && t < T; t += step) {
+        __syncthreads();                                    // the template stores / the previous frame's reads are done
+        const uint8_t *fr = grey + (long)t * HW;
+        const int ox = cx - S - R, oy = cy - S - R;
+        for (int e = lane; e < D * pitch; e += 64) {
+            const int ry = e / pitch, wx = e - ry * pitch;
+            live_region[e] = load4_clamped(fr + (long)clampi(oy + ry, H - 1) * W, ox + 4 * wx, W);
+        }
+        __syncthreads();
+        unsigned long long best = ~0ull;
+        unsigned int bound = limit;                         // min(limit, the lane's best cost)
+        for (int cand = lane; cand < C * C; cand += 64) {
+            const int dyi = cand / C, dxi = cand - dyi * C;
+            const int nx = cx + dxi - S, ny = cy + dyi - S;
+            if (nx < 0 || nx >= W || ny < 0 || ny >= H) continue;
+            const unsigned int *row = live_region + dyi * pitch + (dxi >> 2);
+            const unsigned int sh = dxi & 3;
+            unsigned int cost = 0;
+            for (int j = 0; j < P && cost <= bound; ++j, row += pitch) {
+                unsigned int lo = row[0];
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const unsigned int hi = row[k + 1];
+                    unsigned int v = __builtin_amdgcn_alignbyte(hi, lo, sh);
+                    if (k == K - 1) v &= lastmask;
+                    cost = __builtin_amdgcn_sad_u8(v, tmpl[j * 4 + k], cost);
+                    lo = hi;
+                }
+            }
+            if (cost > bound) continue;
+            bound = cost;
+            const int dx = dxi - S, dy = dyi - S;
+            const unsigned long long key = ((unsigned long long)cost << 30) | ((unsigned long long)(dx * dx + dy * dy) << 16) |
+                                           ((unsigned long long)dyi << 8) | (unsigned long long)dxi;
+            best = key < best ? key : best;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long other = __shfl_xor(best, o, 64);
+            best = other < best ? other : best;
+        }
+        // no candidate within the bound: best is still ~0, whose cost field exceeds every limit
+        const unsigned long long cost = best >> 30;
+        const bool visible = cost <= limit;
+        const int bxi = (int)(best & 255), byi = (int)((best >> 8) & 255);
+        if (visible) {
+            cx += bxi - S;
+            cy += byi - S;
+        }
+        if (lane == 0) {
+            tracks[((long)t * N + n) * 2] = (float)cx;
+            tracks[((long)t * N + n) * 2 + 1] = (float)cy;
+            vis[(long)t * N + n] = visible;
+        }
+        if (visible && (long long)cost <= limit_u) {        // the same decision in every lane
+            __syncthreads();                                // every lane is done with the old template
+            if (lane < P * 4 && tk < K) {
+                const unsigned int *row = live_region + (byi + tj) * pitch + (bxi >> 2) + tk;
+                unsigned int v = __builtin_amdgcn_alignbyte(row[1], row[0], (unsigned int)(bxi & 3));
+                if (tk == K - 1) v &= lastmask;
+                tmpl[lane] = v;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -163,6 +280,29 @@ int s2d_block_track_u8(const uint8_t *grey, int T, int H, int W, const int *poin
     default: return S2D_ERR_ARG;
     }
 #undef S2D_BT
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_block_track_live_u8(const uint8_t *grey, int T, int H, int W, const int *points, int N, int q, int backward, int R, int S,
+                            int tau, int tau_u, float *tracks, uint8_t *vis, hipStream_t stream)
+{
+    if (R < 1 || R > BT_MAX_R || S < 1 || S > BTL_MAX_S || tau < 0 || tau > 255 || tau_u < -1 || tau_u > tau) return S2D_ERR_ARG;
+    if (T < 1 || q < 0 || q >= T || N < 0 || H < 1 || W < 1 || H >= (1 << 15) || W >= (1 << 15)) return S2D_ERR_ARG;
+    if (N == 0) return S2D_OK;
+    const dim3 grid(N, backward && q > 0 ? 2 : 1);
+    const int K = (2 * R + 1 + 3) / 4, pitch = (((2 * S) >> 2) + K + 1) | 1;
+    const size_t lds = (size_t)(2 * (R + S) + 1) * pitch * sizeof(unsigned int);          // at most 143 * 37 * 4 = 21,164 bytes
+#define S2D_BTL(k)                                                                                                              \
+    case k:                                                                                                                     \
+        hipLaunchKernelGGL(block_track_live_kernel<k>, grid, dim3(64), lds, stream, grey, T, H, W, points, N, q, R, S, tau, tau_u, \
+                           tracks, vis);                                                                                        \
+        break;
+    switch (K) {
+        S2D_BTL(1) S2D_BTL(2) S2D_BTL(3) S2D_BTL(4)
+    default: return S2D_ERR_ARG;
+    }
+#undef S2D_BTL
     S2D_CHECK_LAUNCH();
     return S2D_OK;
 }

@@ -11,7 +11,18 @@ updated, so appearance change (lighting, scale, rotation) makes a point invisibl
 of the tracks round them to pixels anyway (s2d_track_point_id_counts) and stage 1 reads only the mean visibility.
 
 The exact rule is in include/s2d_hip.h (s2d_video_grey_u8, s2d_block_track_u8); tests/block_tracker_ref.py restates it in
-numpy, bit for bit."""
+numpy, bit for bit.
+
+    tracker = LiveBlockTracker(radius=5, search=32, tau=12, refresh=4)   # load_tracker("block-live"), --tracker block-live
+
+lifts two of these limits with the same search (s2d_block_track_live_u8, restated in tests/live_tracker_ref.py): `search` goes
+up to 64 pixels, and the template is live -- after a frame where the point is visible with a mean absolute difference of at
+most `refresh`, the patch round the new position becomes the template (-1: never, the fixed template; `tau`: at every visible
+frame).  The defaults are design choices, not tuned on real video: an exhaustive search costs with the number of candidates, so
+search 32 is about 4 times the work of search 16 and search 64 about 15 times; refresh 4 is a third of `tau`, so that only a
+close match may replace the template.  Limits that stay: whole-pixel positions; drift -- a live template can slide off its object
+step by step, and nothing anchors it to the query frame; untextured regions match anywhere; a sudden appearance change above
+`tau` still hides the point; quality against CoTracker is unmeasured."""
 import numpy as np
 import torch
 
@@ -65,7 +76,23 @@ class BlockTracker:
         tracks = torch.empty((1, T, N, 2), device=dev, dtype=torch.float32)
         vis = torch.empty((1, T, N), device=dev, dtype=torch.uint8)
         if N > 0:
-            lib().call("s2d_block_track_u8", self.grey(video), T, H, W, torch.from_numpy(pts).to(dev), N, int(grid_query_frame),
-                       int(bool(backward_tracking)), self.radius, self.search, self.tau, tracks, vis,
-                       torch.cuda.current_stream().cuda_stream)
+            self._track(self.grey(video), T, H, W, torch.from_numpy(pts).to(dev), N, int(grid_query_frame),
+                        int(bool(backward_tracking)), tracks, vis)
         return tracks, vis.bool()
+
+    def _track(self, grey, T, H, W, pts, N, q, backward, tracks, vis):
+        lib().call("s2d_block_track_u8", grey, T, H, W, pts, N, q, backward, self.radius, self.search, self.tau, tracks, vis,
+                   torch.cuda.current_stream().cuda_stream)
+
+
+class LiveBlockTracker(BlockTracker):
+    """BlockTracker (its grid, mask selection and grey-frame cache) with the wide search and the live template of
+    s2d_block_track_live_u8"""
+
+    def __init__(self, radius=5, search=32, tau=12, refresh=4):
+        super().__init__(radius, search, tau)
+        self.refresh = int(refresh)
+
+    def _track(self, grey, T, H, W, pts, N, q, backward, tracks, vis):
+        lib().call("s2d_block_track_live_u8", grey, T, H, W, pts, N, q, backward, self.radius, self.search, self.tau, self.refresh,
+                   tracks, vis, torch.cuda.current_stream().cuda_stream)

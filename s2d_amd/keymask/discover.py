@@ -2,7 +2,8 @@
 
     python -m s2d_amd.keymask.discover --video-base-path D/DAVIS/JPEGImages/480p --mask-base-path M --save-path S \\
         --visibility-maps-output-base V --visibility-clusters-output-base C --annotation-output-path A \\
-        --tracker cotracker --tracker-checkpoint scaled_offline.pth          (or --tracker block: the built-in baseline)
+        --tracker cotracker --tracker-checkpoint scaled_offline.pth          (or --tracker block: the built-in baseline;
+                                  or --tracker block-live [--tracker-options search=48,refresh=-1]: wide search, live template)
 
 Restates keymask_ident/main_keymask_ident.py and its per-video stages with their file names, layouts, JSON contents and
 observable quirks:
@@ -53,8 +54,22 @@ _DATASETS = (("DAVIS", "DAVIS"), ("ytvis2021", "ytvis2021"), ("ytvis2019", "ytvi
              ("VIPSeg", "VIPSeg"), ("MOSE", "MOSE"), ("sa-v", "SA-V"))
 
 
+def parse_tracker_options(text):
+    """'search=48,refresh=-1' -> {"search": 48, "refresh": -1}: comma-separated key=int"""
+    out = {}
+    for item in filter(None, (s.strip() for s in (text or "").split(","))):
+        key, sep, value = (s.strip() for s in item.partition("="))
+        try:
+            if not sep or not key.isidentifier():
+                raise ValueError
+            out[key] = int(value)
+        except ValueError:
+            raise ValueError(f"--tracker-options {text!r}: expected key=int[,key=int...], got {item!r}") from None
+    return out
+
+
 def parse_args(argv=None):
-    """crw_utils.keymask_args (same flags and defaults) + --tracker, --tracker-checkpoint, --dataset-name"""
+    """crw_utils.keymask_args (same flags and defaults) + --tracker, --tracker-options, --tracker-checkpoint, --dataset-name"""
     p = argparse.ArgumentParser(description="Keymask Identification")
     p.add_argument("--workers", default=4, type=int, metavar="N", help="accepted for compatibility; unused")
     p.add_argument("--manualSeed", type=int, default=777, help="manual seed")
@@ -74,7 +89,11 @@ def parse_args(argv=None):
     p.add_argument("--videos-per-job", default=-1, type=int, help="Number of videos to process per job")
     p.add_argument("--debug", default=False, action="store_true", help="Debug mode")
     p.add_argument("--tracker", default="cotracker",
-                   help="'cotracker', 'block' (the built-in block-matching baseline: no package, no weights) or 'pkg.module:factory'")
+                   help="'cotracker', 'block' (the built-in block-matching baseline: no package, no weights), 'block-live' (the same "
+                        "with a search of up to 64 px and a live template) or 'pkg.module:factory'")
+    p.add_argument("--tracker-options", default=None, metavar="KEY=INT[,KEY=INT...]",
+                   help="keyword arguments of the built-in trackers, e.g. 'search=48,refresh=-1' (block: radius, search, tau; "
+                        "block-live: radius, search, tau, refresh)")
     p.add_argument("--tracker-checkpoint", default=None, help="passed to the tracker (CoTracker: scaled_offline.pth)")
     p.add_argument("--dataset-name", default=None, help="dataset name instead of the one detected in --video-base-path")
     return p.parse_args(argv)
@@ -477,7 +496,8 @@ def run(args, tracker=None):
     torch.manual_seed(args.manualSeed)
     dataset_name, split = detect_dataset(args.video_base_path, args.dataset_name)
     vids, masks = video_and_mask_dirs(args.video_base_path, args.mask_base_path, args.job_id, args.videos_per_job)
-    state = _Run(args, tracker if tracker is not None else load_tracker(args.tracker, args.tracker_checkpoint))
+    state = _Run(args, tracker if tracker is not None else load_tracker(args.tracker, args.tracker_checkpoint,
+                                                                             parse_tracker_options(args.tracker_options)))
     counts = {"done": 0, "skipped": 0, "failed": 0}
     for video_path, masks_path in zip(vids, masks):
         name = os.path.basename(video_path)

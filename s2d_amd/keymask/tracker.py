@@ -9,12 +9,33 @@ pred_tracks [1,T,N,2] (x, y) pixels and pred_visibility [1,T,N] bool.
 
 `load_tracker("cotracker", checkpoint)` builds CoTracker's offline predictor as the reference does (:318-328).  CoTracker is
 third party and optional: it is imported only there.  `load_tracker("block")` returns the built-in block-matching baseline
-(block_tracker.BlockTracker: no package, no weights; its limits are stated there).  `load_tracker("pkg.module:attr")` imports a
-factory and calls it (with `checkpoint=` when one is given); that is how tests and other trackers plug in."""
+(block_tracker.BlockTracker: no package, no weights; its limits are stated there) and `load_tracker("block-live")` the same
+search with a wider reach and a live template (block_tracker.LiveBlockTracker).  `options` (a dict, `--tracker-options`) are
+keyword arguments of these two built-in trackers, e.g. {"search": 48, "refresh": -1}; a key the tracker does not have, or
+options for any other tracker, raise ValueError.  `load_tracker("pkg.module:attr")` imports a factory and calls it (with
+`checkpoint=` when one is given); that is how tests and other trackers plug in."""
 import importlib
+import inspect
 
 
-def load_tracker(spec, checkpoint=None):
+def _built_in(cls, spec, options):
+    options = dict(options or {})
+    known = [p for p in inspect.signature(cls.__init__).parameters if p != "self"]
+    unknown = sorted(set(options) - set(known))
+    if unknown:
+        raise ValueError(f"tracker {spec!r} has no option {', '.join(unknown)} (it has {', '.join(known)})")
+    return cls(**options)
+
+
+def load_tracker(spec, checkpoint=None, options=None):
+    if spec == "block":
+        from .block_tracker import BlockTracker
+        return _built_in(BlockTracker, spec, options)
+    if spec == "block-live":
+        from .block_tracker import LiveBlockTracker
+        return _built_in(LiveBlockTracker, spec, options)
+    if options:
+        raise ValueError(f"tracker {spec!r} takes no options: they are for 'block' and 'block-live'")
     if spec == "cotracker":
         try:
             from cotracker.predictor import CoTrackerPredictor
@@ -26,11 +47,8 @@ def load_tracker(spec, checkpoint=None):
         model = CoTrackerPredictor(checkpoint=checkpoint)
         import torch
         return model.cuda() if torch.cuda.is_available() else model
-    if spec == "block":
-        from .block_tracker import BlockTracker
-        return BlockTracker()
     mod, sep, attr = spec.partition(":")
     if not sep or not mod or not attr:
-        raise ValueError(f"tracker spec {spec!r}: expected 'cotracker', 'block' or 'pkg.module:attr'")
+        raise ValueError(f"tracker spec {spec!r}: expected 'cotracker', 'block', 'block-live' or 'pkg.module:attr'")
     factory = getattr(importlib.import_module(mod), attr)
     return factory(checkpoint=checkpoint) if checkpoint is not None else factory()
