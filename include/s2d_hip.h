@@ -743,6 +743,22 @@ int s2d_block_track_u8(const uint8_t *grey, int T, int H, int W, const int *poin
 int s2d_block_track_live_u8(const uint8_t *grey, int T, int H, int W, const int *points, int N, int q, int backward, int R, int S,
                             int tau, int tau_u, float *tracks, uint8_t *vis, hipStream_t stream);
 
+/* The live tracker's search under a zero-mean cost, with a texture gate (keymask/block_tracker.py ZeroMeanBlockTracker, --tracker
+ * block-zm).  Inputs, tracks, vis, clamping of points, border replicate, candidates (|dx|, |dy| <= S, centre inside the frame),
+ * the lexicographic minimum (cost, dx^2 + dy^2, dy, dx), one template per (point, direction), frames t < q without backward
+ * tracking and frame q as in s2d_block_track_live_u8.  With P = 2R+1, n = P^2 and, for a patch X of n bytes,
+ * mean(X) = (2 sum(X) + n) / (2 n) (integer division: the mean, half rounds up),
+ *     zcost(L, X) = sum_i |(L_i - mean(L)) - (X_i - mean(X))|   (< 2^17),      dev(L) = sum_i |L_i - mean(L)|:
+ * a candidate's cost is zcost(L, the patch round the candidate) against the current template L; the point is visible iff
+ * cost <= tau n and then moves there; L becomes the patch round the new c iff visible and cost <= tau_u n (tau_u = -1: never).
+ * Adding one constant to every pixel of a frame adds it to every mean of that frame, so as long as no pixel saturates the
+ * output does not change.  Gate: a point is trackable iff dev(its query-frame patch) >= texture n (texture = 0: every point);
+ * an untrackable point is not searched: tracks[t] = p at every t, vis = 1 at q only.  trackable u8 [N] receives the flag.
+ * One wave per (point, direction); no input makes the kernel read outside grey.  1 <= R <= 7, 1 <= S <= 64, 0 <= tau <= 255,
+ * -1 <= tau_u <= tau, 0 <= texture <= 127, 0 <= q < T, H and W < 2^15; anything else returns S2D_ERR_ARG.  N == 0: no launch. */
+int s2d_block_track_zm_u8(const uint8_t *grey, int T, int H, int W, const int *points, int N, int q, int backward, int R, int S,
+                          int tau, int tau_u, int texture, float *tracks, uint8_t *vis, uint8_t *trackable, hipStream_t stream);
+
 /* ---- timing helpers for the benchmark's per-launch roofline (not on the data path) ------------------------ */
 
 /* HIP events created with hipEventDisableSystemFence (handles are opaque integers, 0 = failure). */

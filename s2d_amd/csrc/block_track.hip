@@ -1,6 +1,6 @@
 // Block-matching point tracker for keymask discovery (s2d_amd/keymask/block_tracker.py): integer SAD search on u8 grey frames.
 // Self-defined (the reference's tracker is CoTracker, third party): a baseline, not a restatement.  Every output is an integer
-// decision, so tests/block_tracker_ref.py and tests/live_tracker_ref.py reproduce the kernels bit for bit.
+// decision, so tests/block_tracker_ref.py, tests/live_tracker_ref.py and tests/zm_tracker_ref.py reproduce the kernels bit for bit.
 //
 //  grey pass   video f32 [T][3][H][W] (RGB, nominally 0..255) -> u8 [T][H][W]: per channel round-half-even of the value clamped
 //              to [0, 255] (NaN -> 0), then (77 r + 150 g + 29 b + 128) >> 8
@@ -11,6 +11,8 @@
 //              otherwise the centre stays and the point keeps searching round its last good position.
 //  live        the tracker with S up to 64 and a template that is rewritten from the frame where the match is good enough
 //              (s2d_block_track_live_u8; described in front of its kernel below)
+//  zero-mean   the live tracker's search with the patch means removed from the cost and a gate on untextured templates
+//              (s2d_block_track_zm_u8; described in front of its kernel below)
 //
 // LDS image: region rows of `pitch` dwords (odd: consecutive rows start on different banks), the row's bytes packed 4 per dword;
 // a patch row that starts at byte b is read as K + 1 aligned dwords from b >> 2 and shifted into place (v_alignbyte_b32), then
@@ -249,6 +251,180 @@ __global__ __launch_bounds__(64) void block_track_live_kernel(const uint8_t *__r
     }
 }
 
+// ---- the zero-mean tracker (s2d_block_track_zm_u8) ---------------------------------------------------------------------------
+// The live kernel's search (one wave per (point, direction), the LDS region image, the aligned-dword read, the packed key, the
+// exact pruning) with another cost: both patches lose their rounded mean first, mean(X) = (2 sum(X) + n) / (2 n), n = (2R+1)^2,
+//     zcost(L, X) = sum_i |(L_i - mean(L)) - (X_i - mean(X))|,
+// so a brightness offset of a whole frame cancels exactly, and a gate: a point whose query-frame template deviates from its own
+// mean by less than texture * n in total (dev(L) = sum_i |L_i - mean(L)|) is not searched at all -- under a zero-mean cost a flat
+// template costs about 0 against every flat patch.
+//
+// Both sides of the difference are kept biased by 255, L_i - mean(L) + 255 and X_i - mean(X) + 255, which lie in 0 .. 510: two
+// pixels per dword as u16 pairs, and v_sad_u16 takes two absolute differences at once.  The template is stored in that form (two
+// dwords per patch dword, pad halves zero).  A candidate first takes its patch sum (v_sad_u8 against zero over the dwords the
+// cost loop reads), then per patch dword two v_perm_b32 -- byte shift, zero extension and, in a row's last dword, clearing of
+// the pad bytes in one instruction each --, two adds of the pair (255 - mean(X)) and two v_sad_u16.  The division by 2 n is a
+// multiplication: 2 sum + n < 2^17 and 2 n <= 450, for which mulhi(x, ceil(2^32 / (2 n))) is the exact quotient.
+//
+// Key: cost <= 510 * 15^2 < 2^17, then d^2, dy + S and dx + S as in the live kernel: 17 + 14 + 8 + 8 = 47 bits.
+__device__ __forceinline__ unsigned int wave_sum(unsigned int v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <int K>
+__global__ __launch_bounds__(64) void block_track_zm_kernel(const uint8_t *__restrict__ grey, int T, int H, int W,
+                                                            const int *__restrict__ points, int N, int q, int R, int S, int tau,
+                                                            int tau_u, int texture, float *__restrict__ tracks,
+                                                            uint8_t *__restrict__ vis, uint8_t *__restrict__ trackable)
+{
+    extern __shared__ unsigned int zm_region[];
+    __shared__ unsigned int tmpl[(2 * BT_MAX_R + 1) * 8];     // row j, patch dword k: u16 pairs of bytes (0, 1) at 8 j + 2 k, (2, 3) behind
+    const int n = blockIdx.x, backward = blockIdx.y, lane = threadIdx.x;
+    const int P = 2 * R + 1, D = 2 * (R + S) + 1, C = 2 * S + 1;
+    const int pitch = (((2 * S) >> 2) + K + 1) | 1;
+    const long HW = (long)H * W;
+    const int px = clampi(points[2 * n], W - 1), py = clampi(points[2 * n + 1], H - 1);
+    const unsigned int nn = (unsigned int)(P * P), magic = 0xFFFFFFFFu / (2 * nn) + 1;   // 2 n is no power of two: ceil(2^32 / 2n)
+    const unsigned int lastmask = 0xFFFFFFFFu >> (8 * (4 * K - P));
+    const bool one = P - 4 * (K - 1) == 1;                    // a row's last dword holds 1 valid byte, otherwise 3
+    const unsigned int padlo = one ? 0x0000FFFFu : 0xFFFFFFFFu, padhi = one ? 0u : 0x0000FFFFu;   // its valid u16 halves
+    const int tj = lane >> 2, tk = lane & 3;                  // the template dword of this lane (lanes below 4 P)
+    const bool tlane = lane < P * 4 && tk < K;
+
+    // the template from this lane's patch dword v (pad bytes zero; 0 in the other lanes); returns dev(L)
+    auto store_template = [&](unsigned int v) -> unsigned int {
+        const unsigned int mean = __umulhi(2 * wave_sum(__builtin_amdgcn_sad_u8(v, 0u, 0u)) + nn, magic);
+        const unsigned int c2 = (255 - mean) * 0x00010001u;
+        const bool last = tk == K - 1;
+        const unsigned int mlo = last ? padlo : 0xFFFFFFFFu, mhi = last ? padhi : 0xFFFFFFFFu;
+        unsigned int dev = 0;
+        if (tlane) {
+            const unsigned int lo = __builtin_amdgcn_perm(0u, v, 0x0c010c00u) + (c2 & mlo);
+            const unsigned int hi = __builtin_amdgcn_perm(0u, v, 0x0c030c02u) + (c2 & mhi);
+            tmpl[tj * 8 + 2 * tk] = lo;
+            tmpl[tj * 8 + 2 * tk + 1] = hi;
+            dev = __builtin_amdgcn_sad_u16(hi, 0x00FF00FFu & mhi, __builtin_amdgcn_sad_u16(lo, 0x00FF00FFu & mlo, 0u));
+        }
+        return wave_sum(dev);
+    };
+
+    unsigned int v0 = 0;
+    if (tlane) {
+        v0 = load4_clamped(grey + (long)q * HW + (long)clampi(py - R + tj, H - 1) * W, px - R + 4 * tk, W);
+        if (tk == K - 1) v0 &= lastmask;
+    }
+    const bool ok = store_template(v0) >= (unsigned int)texture * nn;
+    if (!backward && lane == 0) {
+        for (int t = gridDim.y == 1 ? 0 : q; t <= q; ++t) {
+            tracks[((long)t * N + n) * 2] = (float)px;
+            tracks[((long)t * N + n) * 2 + 1] = (float)py;
+            vis[(long)t * N + n] = t == q;
+        }
+        trackable[n] = ok;
+    }
+    if (!ok) {                                              // the same decision in every lane: the frames of this direction hold p
+        for (int t = (backward ? 0 : q + 1) + lane; t < (backward ? q : T); t += 64) {
+            tracks[((long)t * N + n) * 2] = (float)px;
+            tracks[((long)t * N + n) * 2 + 1] = (float)py;
+            vis[(long)t * N + n] = 0;
+        }
+        return;
+    }
+    int cx = px, cy = py;
+    const int step = backward ? -1 : 1;
+    const unsigned int limit = (unsigned int)tau * nn;
+    const int limit_u = tau_u * (int)nn;                      // negative: never refreshed
+    for (int t = q + step; t >= 0 && t < T; t += step) {
+        __syncthreads();                                    // the template stores / the previous frame's reads are done
+        const uint8_t *fr = grey + (long)t * HW;
+        const int ox = cx - S - R, oy = cy - S - R;
+        for (int e = lane; e < D * pitch; e += 64) {
+            const int ry = e / pitch, wx = e - ry * pitch;
+            zm_region[e] = load4_clamped(fr + (long)clampi(oy + ry, H - 1) * W, ox + 4 * wx, W);
+        }
+        __syncthreads();
+        unsigned long long best = ~0ull;
+        unsigned int bound = limit;                         // min(limit, the lane's best cost)
+        for (int cand = lane; cand < C * C; cand += 64) {
+            const int dyi = cand / C, dxi = cand - dyi * C;
+            const int nx = cx + dxi - S, ny = cy + dyi - S;
+            if (nx < 0 || nx >= W || ny < 0 || ny >= H) continue;
+            const unsigned int *row = zm_region + dyi * pitch + (dxi >> 2);
+            const unsigned int sh = dxi & 3;
+            unsigned int sum = 0;
+            for (int j = 0; j < P; ++j) {
+                const unsigned int *r = row + j * pitch;
+                unsigned int lo = r[0];
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const unsigned int hi = r[k + 1];
+                    unsigned int v = __builtin_amdgcn_alignbyte(hi, lo, sh);
+                    if (k == K - 1) v &= lastmask;
+                    sum = __builtin_amdgcn_sad_u8(v, 0u, sum);
+                    lo = hi;
+                }
+            }
+            // v_perm_b32 selectors over the bytes of hi:lo (0 .. 3 lo, 4 .. 7 hi, 0x0c a zero byte): bytes sh, sh + 1 and
+            // sh + 2, sh + 3 zero-extended to u16 pairs; in a row's last dword the pad bytes come out zero
+            const unsigned int sello = 0x0c000c00u | sh | ((sh + 1) << 16), selhi = 0x0c000c00u | (sh + 2) | ((sh + 3) << 16);
+            const unsigned int lastlo = one ? 0x0c0c0c00u | sh : sello, lasthi = one ? 0x0c0c0c0cu : 0x0c0c0c00u | (sh + 2);
+            const unsigned int c2 = (255 - __umulhi(2 * sum + nn, magic)) * 0x00010001u;
+            const unsigned int c2lo = c2 & padlo, c2hi = c2 & padhi;
+            unsigned int cost = 0;
+            for (int j = 0; j < P && cost <= bound; ++j, row += pitch) {
+                unsigned int lo = row[0];
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const unsigned int hi = row[k + 1];
+                    const bool last = k == K - 1;
+                    const unsigned int a = __builtin_amdgcn_perm(hi, lo, last ? lastlo : sello) + (last ? c2lo : c2);
+                    const unsigned int b = __builtin_amdgcn_perm(hi, lo, last ? lasthi : selhi) + (last ? c2hi : c2);
+                    cost = __builtin_amdgcn_sad_u16(a, tmpl[j * 8 + 2 * k], cost);
+                    cost = __builtin_amdgcn_sad_u16(b, tmpl[j * 8 + 2 * k + 1], cost);
+                    lo = hi;
+                }
+            }
+            if (cost > bound) continue;
+            bound = cost;
+            const int dx = dxi - S, dy = dyi - S;
+            const unsigned long long key = ((unsigned long long)cost << 30) | ((unsigned long long)(dx * dx + dy * dy) << 16) |
+                                           ((unsigned long long)dyi << 8) | (unsigned long long)dxi;
+            best = key < best ? key : best;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long other = __shfl_xor(best, o, 64);
+            best = other < best ? other : best;
+        }
+        // no candidate within the bound: best is still ~0, whose cost field exceeds every limit
+        const unsigned long long cost = best >> 30;
+        const bool visible = cost <= limit;
+        const int bxi = (int)(best & 255), byi = (int)((best >> 8) & 255);
+        if (visible) {
+            cx += bxi - S;
+            cy += byi - S;
+        }
+        if (lane == 0) {
+            tracks[((long)t * N + n) * 2] = (float)cx;
+            tracks[((long)t * N + n) * 2 + 1] = (float)cy;
+            vis[(long)t * N + n] = visible;
+        }
+        if (visible && (long long)cost <= limit_u) {        // the same decision in every lane
+            __syncthreads();                                // every lane is done with the old template
+            unsigned int v = 0;
+            if (tlane) {
+                const unsigned int *row = zm_region + (byi + tj) * pitch + (bxi >> 2) + tk;
+                v = __builtin_amdgcn_alignbyte(row[1], row[0], (unsigned int)(bxi & 3));
+                if (tk == K - 1) v &= lastmask;
+            }
+            store_template(v);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -303,6 +479,30 @@ int s2d_block_track_live_u8(const uint8_t *grey, int T, int H, int W, const int 
     default: return S2D_ERR_ARG;
     }
 #undef S2D_BTL
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_block_track_zm_u8(const uint8_t *grey, int T, int H, int W, const int *points, int N, int q, int backward, int R, int S,
+                          int tau, int tau_u, int texture, float *tracks, uint8_t *vis, uint8_t *trackable, hipStream_t stream)
+{
+    if (R < 1 || R > BT_MAX_R || S < 1 || S > BTL_MAX_S || tau < 0 || tau > 255 || tau_u < -1 || tau_u > tau) return S2D_ERR_ARG;
+    if (texture < 0 || texture > 127) return S2D_ERR_ARG;
+    if (T < 1 || q < 0 || q >= T || N < 0 || H < 1 || W < 1 || H >= (1 << 15) || W >= (1 << 15)) return S2D_ERR_ARG;
+    if (N == 0) return S2D_OK;
+    const dim3 grid(N, backward && q > 0 ? 2 : 1);
+    const int K = (2 * R + 1 + 3) / 4, pitch = (((2 * S) >> 2) + K + 1) | 1;
+    const size_t lds = (size_t)(2 * (R + S) + 1) * pitch * sizeof(unsigned int);          // the live kernel's region
+#define S2D_BTZ(k)                                                                                                              \
+    case k:                                                                                                                     \
+        hipLaunchKernelGGL(block_track_zm_kernel<k>, grid, dim3(64), lds, stream, grey, T, H, W, points, N, q, R, S, tau, tau_u, \
+                           texture, tracks, vis, trackable);                                                                    \
+        break;
+    switch (K) {
+        S2D_BTZ(1) S2D_BTZ(2) S2D_BTZ(3) S2D_BTZ(4)
+    default: return S2D_ERR_ARG;
+    }
+#undef S2D_BTZ
     S2D_CHECK_LAUNCH();
     return S2D_OK;
 }

@@ -22,7 +22,21 @@ frame).  The defaults are design choices, not tuned on real video: an exhaustive
 search 32 is about 4 times the work of search 16 and search 64 about 15 times; refresh 4 is a third of `tau`, so that only a
 close match may replace the template.  Limits that stay: whole-pixel positions; drift -- a live template can slide off its object
 step by step, and nothing anchors it to the query frame; untextured regions match anywhere; a sudden appearance change above
-`tau` still hides the point; quality against CoTracker is unmeasured."""
+`tau` still hides the point; quality against CoTracker is unmeasured.
+
+    tracker = ZeroMeanBlockTracker(radius=5, search=32, tau=12, refresh=-1, texture=4)   # load_tracker("block-zm"), --tracker block-zm
+
+is the live tracker's search under another cost (s2d_block_track_zm_u8, restated in tests/zm_tracker_ref.py): both patches lose
+their rounded mean before the absolute differences are summed, so a brightness offset of a whole frame (auto-exposure, a cloud, a
+fade) cancels exactly as long as no pixel saturates, and `tau` and `refresh` bound the mean absolute zero-mean difference.  Under
+such a cost a flat template costs about 0 against every flat patch, so a point whose query-frame patch deviates from its own mean
+by less than `texture` grey levels on average is refused: with `texture` > 0 such points are not tracked and their columns are
+left out of pred_tracks and pred_visibility (0 keeps every point).  The defaults are design choices, not tuned on real video:
+refresh -1 because the fixed template is anchored to the query frame and cannot drift, and the zero-mean cost is what lets it
+survive a lighting change; texture 4 because it is a third of `tau`, so a template must deviate from its mean by a margin before
+a `tau`-sized mismatch means anything.  Keymask discovery reads the visibility in stage 1 only; stage 2 ignores it, so what this
+tracker changes there is the positions, and which points exist at all.  Limits that stay: whole-pixel positions; a change of gain
+(contrast) is not removed, only an offset; scale and rotation; repeated texture; quality against CoTracker is unmeasured."""
 import numpy as np
 import torch
 
@@ -76,13 +90,15 @@ class BlockTracker:
         tracks = torch.empty((1, T, N, 2), device=dev, dtype=torch.float32)
         vis = torch.empty((1, T, N), device=dev, dtype=torch.uint8)
         if N > 0:
-            self._track(self.grey(video), T, H, W, torch.from_numpy(pts).to(dev), N, int(grid_query_frame),
-                        int(bool(backward_tracking)), tracks, vis)
+            tracks, vis = self._track(self.grey(video), T, H, W, torch.from_numpy(pts).to(dev), N, int(grid_query_frame),
+                                      int(bool(backward_tracking)), tracks, vis)
         return tracks, vis.bool()
 
     def _track(self, grey, T, H, W, pts, N, q, backward, tracks, vis):
+        """fills tracks [1,T,N,2] and vis [1,T,N] (u8) and returns them, or the columns of them that the tracker keeps"""
         lib().call("s2d_block_track_u8", grey, T, H, W, pts, N, q, backward, self.radius, self.search, self.tau, tracks, vis,
                    torch.cuda.current_stream().cuda_stream)
+        return tracks, vis
 
 
 class LiveBlockTracker(BlockTracker):
@@ -96,3 +112,22 @@ class LiveBlockTracker(BlockTracker):
     def _track(self, grey, T, H, W, pts, N, q, backward, tracks, vis):
         lib().call("s2d_block_track_live_u8", grey, T, H, W, pts, N, q, backward, self.radius, self.search, self.tau, self.refresh,
                    tracks, vis, torch.cuda.current_stream().cuda_stream)
+        return tracks, vis
+
+
+class ZeroMeanBlockTracker(BlockTracker):
+    """BlockTracker (its grid, mask selection and grey-frame cache) with the zero-mean cost and the texture gate of
+    s2d_block_track_zm_u8"""
+
+    def __init__(self, radius=5, search=32, tau=12, refresh=-1, texture=4):
+        super().__init__(radius, search, tau)
+        self.refresh, self.texture = int(refresh), int(texture)
+
+    def _track(self, grey, T, H, W, pts, N, q, backward, tracks, vis):
+        trackable = torch.empty((N,), device=tracks.device, dtype=torch.uint8)
+        lib().call("s2d_block_track_zm_u8", grey, T, H, W, pts, N, q, backward, self.radius, self.search, self.tau, self.refresh,
+                   self.texture, tracks, vis, trackable, torch.cuda.current_stream().cuda_stream)
+        if self.texture <= 0:
+            return tracks, vis
+        keep = trackable.bool()                             # the select reads the number of kept points back
+        return tracks[:, :, keep], vis[:, :, keep]

@@ -3,7 +3,8 @@
     python -m s2d_amd.keymask.discover --video-base-path D/DAVIS/JPEGImages/480p --mask-base-path M --save-path S \\
         --visibility-maps-output-base V --visibility-clusters-output-base C --annotation-output-path A \\
         --tracker cotracker --tracker-checkpoint scaled_offline.pth          (or --tracker block: the built-in baseline;
-                                  or --tracker block-live [--tracker-options search=48,refresh=-1]: wide search, live template)
+                                  or --tracker block-live [--tracker-options search=48,refresh=-1]: wide search, live template;
+                                  or --tracker block-zm [--tracker-options search=48,texture=0]: zero-mean cost, texture gate)
 
 Restates keymask_ident/main_keymask_ident.py and its per-video stages with their file names, layouts, JSON contents and
 observable quirks:
@@ -90,10 +91,11 @@ def parse_args(argv=None):
     p.add_argument("--debug", default=False, action="store_true", help="Debug mode")
     p.add_argument("--tracker", default="cotracker",
                    help="'cotracker', 'block' (the built-in block-matching baseline: no package, no weights), 'block-live' (the same "
-                        "with a search of up to 64 px and a live template) or 'pkg.module:factory'")
+                        "with a search of up to 64 px and a live template), 'block-zm' (that search with a zero-mean cost, which a "
+                        "change of brightness does not disturb, and a texture gate) or 'pkg.module:factory'")
     p.add_argument("--tracker-options", default=None, metavar="KEY=INT[,KEY=INT...]",
                    help="keyword arguments of the built-in trackers, e.g. 'search=48,refresh=-1' (block: radius, search, tau; "
-                        "block-live: radius, search, tau, refresh)")
+                        "block-live: radius, search, tau, refresh; block-zm: radius, search, tau, refresh, texture)")
     p.add_argument("--tracker-checkpoint", default=None, help="passed to the tracker (CoTracker: scaled_offline.pth)")
     p.add_argument("--dataset-name", default=None, help="dataset name instead of the one detected in --video-base-path")
     return p.parse_args(argv)

@@ -10,8 +10,9 @@ pred_tracks [1,T,N,2] (x, y) pixels and pred_visibility [1,T,N] bool.
 `load_tracker("cotracker", checkpoint)` builds CoTracker's offline predictor as the reference does (:318-328).  CoTracker is
 third party and optional: it is imported only there.  `load_tracker("block")` returns the built-in block-matching baseline
 (block_tracker.BlockTracker: no package, no weights; its limits are stated there) and `load_tracker("block-live")` the same
-search with a wider reach and a live template (block_tracker.LiveBlockTracker).  `options` (a dict, `--tracker-options`) are
-keyword arguments of these two built-in trackers, e.g. {"search": 48, "refresh": -1}; a key the tracker does not have, or
+search with a wider reach and a live template (block_tracker.LiveBlockTracker), and `load_tracker("block-zm")` that search under
+a zero-mean cost with a texture gate (block_tracker.ZeroMeanBlockTracker), which a change of brightness does not disturb.
+`options` (a dict, `--tracker-options`) are keyword arguments of these built-in trackers, e.g. {"search": 48, "refresh": -1}; a key the tracker does not have, or
 options for any other tracker, raise ValueError.  `load_tracker("pkg.module:attr")` imports a factory and calls it (with
 `checkpoint=` when one is given); that is how tests and other trackers plug in."""
 import importlib
@@ -34,8 +35,11 @@ def load_tracker(spec, checkpoint=None, options=None):
     if spec == "block-live":
         from .block_tracker import LiveBlockTracker
         return _built_in(LiveBlockTracker, spec, options)
+    if spec == "block-zm":
+        from .block_tracker import ZeroMeanBlockTracker
+        return _built_in(ZeroMeanBlockTracker, spec, options)
     if options:
-        raise ValueError(f"tracker {spec!r} takes no options: they are for 'block' and 'block-live'")
+        raise ValueError(f"tracker {spec!r} takes no options: they are for 'block', 'block-live' and 'block-zm'")
     if spec == "cotracker":
         try:
             from cotracker.predictor import CoTrackerPredictor
@@ -49,6 +53,6 @@ def load_tracker(spec, checkpoint=None, options=None):
         return model.cuda() if torch.cuda.is_available() else model
     mod, sep, attr = spec.partition(":")
     if not sep or not mod or not attr:
-        raise ValueError(f"tracker spec {spec!r}: expected 'cotracker', 'block', 'block-live' or 'pkg.module:attr'")
+        raise ValueError(f"tracker spec {spec!r}: expected 'cotracker', 'block', 'block-live', 'block-zm' or 'pkg.module:attr'")
     factory = getattr(importlib.import_module(mod), attr)
     return factory(checkpoint=checkpoint) if checkpoint is not None else factory()
