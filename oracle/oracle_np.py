@@ -53,7 +53,8 @@ def _c(a, dt):
 # SOLVER.AMP.ENABLED True) with both operands of every linear / convolution / einsum rounded to fp16 (nearest-even, as `.half()`)
 # and f32 accumulation -- the R50 trunk, the video decoder's linear layers, the mask-logit einsum.  The pixel decoder and the
 # matcher run in fp32 in the reference (msdeformattn.py:314, matcher.py:266-268).  `AMP = True` arms it; resnet50() and
-# video_decoder() switch the rounding on for their own extent.
+# video_decoder() switch the rounding on for their own extent.  fp16 subnormals are kept, not flushed, as numpy's astype keeps them: the
+# device does the same (s2d_amd/csrc/gemm_amp.hip's header; tests/test_gpu_amp_forms.py::test_fp16_subnormal_operands holds both to it).
 AMP = False
 _AMP_ON = [False]
 

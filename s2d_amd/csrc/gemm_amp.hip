@@ -1,6 +1,9 @@
 // Dense contractions with fp16 OPERANDS and f32 accumulate / f32 OUTPUT ("autocast-like"; SOLVER.AMP.ENABLED True in every shipped
 // yaml; engine/train_loop.py:709 `with autocast():`): both operands rounded to fp16 (round-to-nearest-even, as `.half()`), products
-// accumulated in f32 by ONE v_mfma_f32_32x32x16_f16 per tile and k-step, f32 out.  This is NOT bit-for-bit what torch.autocast
+// accumulated in f32 by ONE v_mfma_f32_32x32x16_f16 per tile and k-step, f32 out.  The rounding is the whole of IEEE binary16: ties go to the
+// even mantissa, magnitudes from 65520 on become inf, NaN stays NaN, and fp16 SUBNORMALS ARE KEPT -- v_cvt_f16_f32 produces them and on gfx950
+// the MFMA multiplies a subnormal operand at its exact value, neither operand is flushed (measured bit for bit against one-hot operands:
+// tests/test_gpu_amp_forms.py, figures in profiles/amp_parity.txt; oracle_np._r16 restates the same rule).  This is NOT bit-for-bit what torch.autocast
 // computes: real autocast also rounds every OUTPUT to fp16 (so FrozenBN, residual adds and ReLUs of the trunk run on fp16 tensors)
 // and runs the attention bmm's in fp16; here activations stay f32 between layers.  The AMP parity tests therefore pin this mode
 // against the oracle's restatement of THIS definition (oracle_np.AMP), not against a recording of torch.autocast.  Opt-in, for the modules

@@ -89,11 +89,29 @@ def set_amp_compute(model, enabled=True):
     the R50 trunk, the video decoder's linear layers and the mask-logit einsum -- take single-pass fp16 MFMA arithmetic (operands
     rounded to fp16, f32 accumulation) in the forward / loss path; the pixel decoder and the criterion stay fp32-class, as the
     reference forces them to (msdeformattn.py:314, matcher.py:266-268).  Default off: the library computes in fp32-class
-    arithmetic whatever the autocast state.  Returns the model."""
+    arithmetic whatever the autocast state.  forward_losses only: forward_backward is fp32-class throughout whatever this says -- the
+    gradient kernels differentiate the fp32-class forward, so its taped student ignores the flag and its teacher runs with the flag
+    held off (_AmpComputeOff): losses and gradients of a training iteration do not depend on it.  Returns the model."""
     for m in model.modules():
         if isinstance(m, (ResNet50, VideoMultiScaleMaskedTransformerDecoder)):
             m.amp = bool(enabled)
     return model
+
+
+class _AmpComputeOff:
+    """`with _AmpComputeOff(net):` -- the forwards of `net` inside run fp32-class; the modules' amp flags come back on exit"""
+
+    def __init__(self, net):
+        self.mods = [m for m in net.modules() if isinstance(m, (ResNet50, VideoMultiScaleMaskedTransformerDecoder))]
+
+    def __enter__(self):
+        self.saved = [m.amp for m in self.mods]
+        for m in self.mods:
+            m.amp = False
+
+    def __exit__(self, *a):
+        for m, v in zip(self.mods, self.saved):
+            m.amp = v
 
 
 def _test_kwargs(mf, npred_name, eval_student=False):
@@ -503,7 +521,8 @@ class KDVideoMaskFormer(nn.Module):
         else:
             side = main
         with torch.cuda.stream(side):
-            teacher = self.teacher(images, True, aux_masks=self.teacher_aux_masks)
+            with _AmpComputeOff(self.teacher):                     # the iteration is fp32-class throughout (set_amp_compute)
+                teacher = self.teacher(images, True, aux_masks=self.teacher_aux_masks)
             tgt, cnt, kept, ne, lab = ops.kd_targets(teacher.class_logits[-1], teacher.mask_logits[-1], teacher.dims, Hp, Wp, kd_nmax,
                                                 self.score_threshold_distillation, self.num_predictions_distillation, want_labels=True)
             if self.distillation_nms:

@@ -123,7 +123,10 @@ def gemm_nt(A, B, scale=None, bias=None, res=None, relu=False, out=None, res_row
     A may be 2-D or batched 3-D; B 2-D (shared) or 3-D (per batch).  res_rows > 0: res is [res_rows, ldr] and row r of the
     output receives res[r % res_rows]; res_cols > 0: only the first res_cols columns receive it (ldr = res.shape[-1]).
     dropout = (p, seed, site[, row0]): act(dropout_p(A @ B^T + bias) + res) with the counter-based mask of csrc/dropout.h fused into
-    the epilogue (2-D operands, N % 8 == 0)."""
+    the epilogue (2-D operands, N % 8 == 0).
+    K % 4 == 0 in every mode.  Inside amp_fp16 a res_cols that is no multiple of 4 is refused (RuntimeError from
+    s2d_gemm_nt_amp_f32, nothing launched), where the fp32-class launch takes it through its scalar epilogue: no AMP module has
+    such a residual, and the call is not rerouted to other arithmetic behind the caller's back."""
     for t in (A, B, scale, bias, res, out):
         _chk(t)
     if dropout is not None and dropout[0] > 0.0:
