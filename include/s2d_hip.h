@@ -488,6 +488,19 @@ int s2d_mask_plane_bbox_u32(const uint32_t *bits, int F, int H, int W, long word
 int s2d_mask_cross_counts_u64(const uint32_t *a, int D, const uint32_t *b, int G, long words, unsigned long long *inter,
                               hipStream_t stream);
 
+/* Boundary band of F bit planes bits [F][ceil(H*W/32)] (the layout above; rows are not word-aligned unless W % 32 == 0), as
+ * Boundary IoU defines it (Cheng et al., CVPR 2021; the published mask_to_boundary routine, restated): out = M & ~E, where
+ * E is M eroded d times by a 3 x 3 square with everything outside the image counting as 0 -- one erosion by a
+ * (2d+1) x (2d+1) square with a zero border, so every mask pixel within d of the image edge is boundary.  Valid for any
+ * H, W >= 1 with H*W < 2^31 and any d >= 1 (2d+1 > min(H, W): E is empty and out = the mask); F times the tiles of a plane
+ * (ceil(W/1024) word columns x about H/128 row bands at most) must stay below 2^31.  Input bits of a plane's last word at and
+ * beyond H*W are ignored and written 0.  out [F][ceil(H*W/32)] may not alias bits; bitwise deterministic.
+ * workspace: s2d_mask_boundary_workspace_words(F, H, W, d) words, 0 (workspace may be null) unless min(d, (min(H,W)+1)/2) > 64:
+ * larger radii chain erosions of at most 64 through it.  The query returns -1 for arguments the call refuses. */
+long s2d_mask_boundary_workspace_words(int F, int H, int W, int d);
+int s2d_mask_boundary_bits_u32(const uint32_t *bits, int F, int H, int W, int d, uint32_t *workspace, long workspace_words,
+                               uint32_t *out, hipStream_t stream);
+
 /* ---- test-time frame resize (s2d_amd/data/resize.py, data/test_loader.py): detectron2 ResizeTransform.apply_image =
  * PIL Image.resize(BILINEAR) on uint8 RGB frames, bit-exact ------------------------------------------------------------- */
 

@@ -1,0 +1,214 @@
+// Mask -> boundary band on bit planes, the per-pixel work of Boundary AP (s2d_amd/ytvis_eval.py; Cheng et al., "Boundary IoU",
+// CVPR 2021, and the published mask_to_boundary routine, restated): Bd = M & ~E, where E is M eroded d times by a 3 x 3 square
+// with everything outside the image counting as 0.  d such erosions are one erosion by a (2d+1) x (2d+1) square with a zero
+// border, and that square is separable:  E[y][x] = AND_{|dy| <= d} Eh[y + dy][x],  Eh[y][x] = AND_{|dx| <= d} M[y][x + dx].
+//
+// Planes are flat (pixel i -> word i/32, bit i%32: rows are not word-aligned unless W % 32 == 0); the kernel works on
+// ROW-ALIGNED words (row y, word k = pixels 32k .. 32k+31 of that row, pixels at and beyond W zero).
+//
+//   erode_tile_kernel   one workgroup per tile of TR rows x TW row-aligned words of one plane, r <= 64:
+//     1. horizontal, in registers: for every word of the tile and of its r halo rows above and below, the 192 row bits
+//        around it (pixels 32k-64 .. 32k+127, seven flat words funnelled into three u64, pixels outside the row masked to
+//        0: that is the zero border, and it drops whatever sits in a plane's padding bits) are ANDed over a window of
+//        n = 2r+1 bits by doubling: A_1 = V, A_2a = A_a & (A_a >> a) up to the largest power of two p <= n, then
+//        A_p & (A_p >> (n - p)) -- AND is idempotent, so two overlapping windows of p make one of n.  The word goes to LDS;
+//        halo rows outside the image are 0.
+//     2. vertical, in LDS: the same doubling over rows as plain word ANDs, ping-pong between two buffers (flat indices,
+//        adjacent lanes on adjacent words: no bank conflicts), one barrier per step.
+//     3. M & ~E (or E itself for an intermediate pass), written back to the flat layout: plain stores when rows are
+//        word-aligned, otherwise each row-aligned word is ORed into the one or two flat words it covers (out zeroed first;
+//        only pixel bits are ever set, so a plane's padding bits stay 0).  OR commutes: the result is bitwise deterministic.
+//
+// d > 64 (frames beyond 4K at the default ratio) chains erosions: squares add up, erode(r1 + r2) = erode(r2) o erode(r1),
+// also with the zero border (an eroded plane is zero outside the image like its input).  The intermediates alternate between
+// the caller's workspace and `out`, the last one in the workspace.  A window that does not fit the image (2d+1 > min(H, W))
+// leaves E empty whatever d is, so d is first clamped to (min(H, W) + 1) / 2: no frame of the evaluator needs a second pass.
+#include "common.h"
+
+namespace {
+
+constexpr int BD_T = 256;
+constexpr int BD_RMAX = 64;         // one pass: the 192-bit window holds 64 pixels either side of a word
+constexpr int BD_CAP = 8192;        // words per LDS buffer (two buffers: 64 KiB, two workgroups per CU)
+constexpr int BD_TW = 32;           // row-aligned words per tile row at most
+
+struct u192 { unsigned long long a, b, c; };   // bit i of the window: a = 0..63, b = 64..127, c = 128..191
+
+// bits i + s -> i, zeros in at the top; 1 <= s <= 64
+__device__ __forceinline__ u192 shr192(u192 v, int s)
+{
+    u192 o;
+    if (s == 64) { o.a = v.b; o.b = v.c; o.c = 0ull; return o; }
+    o.a = (v.a >> s) | (v.b << (64 - s));
+    o.b = (v.b >> s) | (v.c << (64 - s));
+    o.c = v.c >> s;
+    return o;
+}
+__device__ __forceinline__ u192 and192(u192 x, u192 y) { u192 o = {x.a & y.a, x.b & y.b, x.c & y.c}; return o; }
+
+// bits [lo, hi) of a 64-bit chunk whose first bit is window bit `base`
+__device__ __forceinline__ unsigned long long chunk_mask(int lo, int hi, int base)
+{
+    int a = lo - base, b = hi - base;
+    a = a < 0 ? 0 : a;
+    b = b > 64 ? 64 : b;
+    if (b <= a) return 0ull;
+    const unsigned long long upto = b == 64 ? ~0ull : (1ull << b) - 1ull;
+    return upto & ~((1ull << a) - 1ull);                 // a < b <= 64: the shift is defined
+}
+
+// pixels 32k-64 .. 32k+127 of row y of a flat plane, pixels outside [0, W) zero
+__device__ __forceinline__ u192 row_window(const uint32_t *__restrict__ pl, long wpf, int y, int W, int k)
+{
+    const int x0 = 32 * k - 64;
+    const long P = (long)y * W + x0;                        // flat bit of window bit 0: >= -64
+    const long wb = P >> 5;                                 // floor, also below zero
+    const int o = (int)(P & 31);
+    unsigned int g[7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) g[j] = (wb + j >= 0 && wb + j < wpf) ? pl[wb + j] : 0u;
+    unsigned int v[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) v[j] = (unsigned int)(((((unsigned long long)g[j + 1]) << 32) | g[j]) >> o);
+    const int lo = x0 < 0 ? -x0 : 0;
+    const int hi = W - x0 < 192 ? W - x0 : 192;
+    u192 w;
+    w.a = ((((unsigned long long)v[1]) << 32) | v[0]) & chunk_mask(lo, hi, 0);
+    w.b = ((((unsigned long long)v[3]) << 32) | v[2]) & chunk_mask(lo, hi, 64);
+    w.c = ((((unsigned long long)v[5]) << 32) | v[4]) & chunk_mask(lo, hi, 128);
+    return w;
+}
+
+// pixels 32k .. 32k+31 of row y, pixels at and beyond W zero
+__device__ __forceinline__ unsigned int row_word(const uint32_t *__restrict__ pl, long wpf, int y, int W, int k)
+{
+    const long P = (long)y * W + 32 * k;
+    const long wb = P >> 5;
+    const int o = (int)(P & 31);
+    const unsigned int g0 = pl[wb];
+    const unsigned int g1 = wb + 1 < wpf ? pl[wb + 1] : 0u;
+    const unsigned int v = (unsigned int)(((((unsigned long long)g1) << 32) | g0) >> o);
+    const int n = W - 32 * k;
+    return n >= 32 ? v : (v & ((1u << n) - 1u));            // 1 <= n: the word starts inside the row
+}
+
+// src: planes to erode by r; orig: planes M for the last pass (dst = M & ~E) or null (dst = E).  Workgroup b: plane
+// b / (ntx * nty), row tile (b / ntx) % nty, word tile b % ntx.  Dynamic LDS: 2 * TW * (TR + 2r) words.
+__global__ __launch_bounds__(BD_T) void erode_tile_kernel(const uint32_t *__restrict__ src, const uint32_t *__restrict__ orig,
+                                                          uint32_t *__restrict__ dst, int H, int W, int r, long wpf, int S,
+                                                          int TW, int TR, int ntx, int nty, int aligned)
+{
+    extern __shared__ unsigned int lds[];
+    const unsigned int nb = (unsigned int)ntx * nty;
+    const unsigned int f = blockIdx.x / nb, t = blockIdx.x - f * nb;
+    const int ty = t / ntx, tx = t - ty * ntx;
+    const int y0 = ty * TR, k0 = tx * TW;
+    const int LR = TR + 2 * r, N = TW * LR;
+    const int n = 2 * r + 1;
+    int p = 2;
+    while (2 * p <= n) p *= 2;                              // largest power of two <= n (n >= 3)
+    const uint32_t *pl = src + (long)f * wpf;
+    unsigned int *cur = lds, *nxt = lds + N;
+
+    for (int i = threadIdx.x; i < N; i += BD_T) {
+        const int ry = i / TW, k = k0 + (i - ry * TW), y = y0 - r + ry;
+        unsigned int e = 0u;
+        if (y >= 0 && y < H && k < S) {
+            u192 A = row_window(pl, wpf, y, W, k);
+            for (int a = 1; a < p; a <<= 1) A = and192(A, shr192(A, a));
+            A = and192(A, shr192(A, n - p));                // window bit q = AND of pixels q .. q + 2r of the window
+            const int pos = 64 - r;                         // pixel 32k + j is the centre of the window that starts at 64 + j - r
+            e = pos == 0 ? (unsigned int)A.a : (unsigned int)((A.a >> pos) | (A.b << (64 - pos)));
+        }
+        cur[i] = e;
+    }
+    __syncthreads();
+    for (int a = 1; a < p; a <<= 1) {                       // rows: cur[row q] = AND of Eh rows q .. q + a - 1
+        const int sh = a * TW;
+        for (int i = threadIdx.x; i < N; i += BD_T) nxt[i] = i + sh < N ? (cur[i] & cur[i + sh]) : 0u;
+        __syncthreads();
+        unsigned int *s = cur; cur = nxt; nxt = s;
+    }
+    const int sh = (n - p) * TW;
+    uint32_t *op = dst + (long)f * wpf;
+    const uint32_t *ml = orig ? orig + (long)f * wpf : nullptr;
+    for (int i = threadIdx.x; i < TR * TW; i += BD_T) {      // output row y0 + ry: window rows ry .. ry + 2r of the tile
+        const int ry = i / TW, k = k0 + (i - ry * TW), y = y0 + ry;
+        if (y >= H || k >= S) continue;
+        unsigned int v = cur[i] & cur[i + sh];              // i + sh <= (TR - 1 + 2r) * TW + TW - 1 < N
+        if (ml) v = row_word(ml, wpf, y, W, k) & ~v;
+        const long P = (long)y * W + 32 * k;
+        if (aligned) {
+            op[P >> 5] = v;
+        } else if (v) {
+            const int o = (int)(P & 31);
+            atomicOr(&op[P >> 5], v << o);                  // set bits are pixels of the plane: the words exist
+            const unsigned int hi = o ? v >> (32 - o) : 0u;
+            if (hi) atomicOr(&op[(P >> 5) + 1], hi);
+        }
+    }
+}
+
+struct BdPlan { int d, TW, TR, ntx, nty, S; long wpf, nb; };
+
+// d clamped to where E is empty anyway; the tile: at most BD_TW words wide (rows of more words are cut evenly), as many
+// rows as one LDS buffer holds beside the 2r halo rows (>= 128), cut evenly over H
+bool bd_plan(int F, int H, int W, int d, BdPlan *pp)
+{
+    if (F < 0 || H < 1 || W < 1 || d < 1 || (long)H * W >= (1L << 31)) return false;
+    BdPlan q;
+    const int m = H < W ? H : W;
+    q.d = d < (m + 1) / 2 ? d : (m + 1) / 2;
+    q.wpf = ((long)H * W + 31) / 32;
+    q.S = (W + 31) / 32;
+    q.ntx = cdiv(q.S, BD_TW);
+    q.TW = cdiv(q.S, q.ntx);
+    const int r = q.d < BD_RMAX ? q.d : BD_RMAX;             // the widest pass
+    const int tr_max = BD_CAP / q.TW - 2 * r;
+    q.nty = cdiv(H, tr_max);
+    q.TR = cdiv(H, q.nty);
+    q.nb = (long)q.ntx * q.nty;
+    if ((long)F * q.nb >= (1L << 31)) return false;
+    *pp = q;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+long s2d_mask_boundary_workspace_words(int F, int H, int W, int d)
+{
+    BdPlan q;
+    if (!bd_plan(F, H, W, d, &q)) return -1;
+    return q.d <= BD_RMAX ? 0 : (long)F * q.wpf;
+}
+
+int s2d_mask_boundary_bits_u32(const uint32_t *bits, int F, int H, int W, int d, uint32_t *workspace, long workspace_words,
+                               uint32_t *out, hipStream_t stream)
+{
+    BdPlan q;
+    if (!bits || !out || bits == out || !bd_plan(F, H, W, d, &q)) return S2D_ERR_ARG;
+    const long need = q.d <= BD_RMAX ? 0 : (long)F * q.wpf;
+    if (need && (!workspace || workspace_words < need || workspace == out || workspace == bits)) return S2D_ERR_ARG;
+    if (F == 0) return S2D_OK;
+    const int aligned = (W & 31) == 0;
+    const int passes = cdiv(q.d, BD_RMAX);
+    const uint32_t *src = bits;
+    int left = q.d;
+    for (int j = 1; j <= passes; ++j) {
+        const int r = left < BD_RMAX ? left : BD_RMAX;
+        left -= r;
+        const bool last = j == passes;
+        uint32_t *dst = last || ((passes - 1 - j) & 1) ? out : workspace;     // the last intermediate lies in the workspace
+        if (!aligned && s2d_zero_async(dst, sizeof(uint32_t) * (size_t)F * q.wpf, stream) != S2D_OK) return S2D_ERR_LAUNCH;
+        const size_t lds = sizeof(unsigned int) * 2 * (size_t)q.TW * (q.TR + 2 * r);
+        hipLaunchKernelGGL(erode_tile_kernel, dim3((unsigned)(F * q.nb)), dim3(BD_T), lds, stream, src, last ? bits : nullptr, dst, H, W,
+                           r, q.wpf, q.S, q.TW, q.TR, q.ntx, q.nty, aligned);
+        S2D_CHECK_LAUNCH();
+        src = dst;
+    }
+    return S2D_OK;
+}
+
+}  // extern "C"

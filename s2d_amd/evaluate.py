@@ -7,7 +7,8 @@ key conversions (checkpoint.load_checkpoint; every tensor of the evaluated netwo
 split through `model([inputs])` with the test loader (data/test_loader.py) and YTVISEvaluator.process.  Predictions stay on the
 device until they are COCO RLE (the meta-arch's inference_rle switch); labels map to the GT file's category ids in sorted order, as
 the registered dataset's metadata maps them.  Writes OUT/results.json (the reference layout),
-OUT/metrics.json (the "segm" dict; not for a split without annotations) and prints one JSON timing line: videos/s, frames/s, the
+OUT/metrics.json (the "segm" dict; with --boundary-ap {"segm": ..., "boundary": ...}, Boundary AP beside mask AP from the same
+pass over the videos; not for a split without annotations) and prints one JSON timing line: videos/s, frames/s, the
 number of windows run (one per video unless MODEL.MASK_FORMER.TEST.WINDOW_INFERENCE cuts long videos) and the fraction of the wall
 time the model waited on the loader.  Under torch.distributed.run the videos are split round-robin by
 rank and rank 0 writes the files."""
@@ -30,6 +31,8 @@ def parse_args(argv=None):
     ap.add_argument("--threads", type=int, default=8, help="JPEG decode threads (<= 16)")
     ap.add_argument("--prefetch", type=int, default=2, help="videos decoded ahead (1 or 2)")
     ap.add_argument("--dist-backend", default="gloo", help="process group backend under torch.distributed.run")
+    ap.add_argument("--boundary-ap", action="store_true", help="also score Boundary AP (matching on min(mask IoU, boundary IoU))")
+    ap.add_argument("--dilation-ratio", type=float, default=0.02, help="boundary band width as a fraction of the image diagonal")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="config overrides KEY VALUE ...")
     return ap.parse_args(argv)
 
@@ -50,9 +53,10 @@ def build_model(cfg, weights, device):
     return model
 
 
-def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, prefetch=2):
+def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, prefetch=2, boundary=False, dilation_ratio=0.02):
     """score `model` on a YTVIS split: every video through `model([inputs])` (eval mode, predictions as COCO RLE) with the test
-    loader and YTVISEvaluator; writes output_dir/results.json and, on rank 0 of a split with annotations, output_dir/metrics.json.
+    loader and YTVISEvaluator; writes output_dir/results.json and, on rank 0 of a split with annotations, output_dir/metrics.json
+    (boundary: Boundary AP as well, and metrics.json holds {"segm", "boundary"}).
     The model's training mode and inference_rle switch are restored afterwards.  -> (results, timing line dict)"""
     from .data.test_loader import YTVISTestLoader
     from .ytvis_eval import YTVISEvaluator
@@ -63,7 +67,8 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
             gt = json.load(fh)
     # labels -> dataset category ids as the registered dataset's metadata maps them (load_ytvis_json: sorted ids, contiguous)
     id_map = {c: i for i, c in enumerate(sorted(c["id"] for c in gt.get("categories", [])))} or None
-    evaluator = YTVISEvaluator(json_file=gt, distributed=True, output_dir=output_dir, dataset_id_to_contiguous_id=id_map)
+    evaluator = YTVISEvaluator(json_file=gt, distributed=True, output_dir=output_dir, dataset_id_to_contiguous_id=id_map,
+                               boundary=boundary, dilation_ratio=dilation_ratio)
     evaluator.reset()
     loader = YTVISTestLoader.from_config(cfg, gt, image_root, device=device, threads=threads, prefetch=prefetch)
 
@@ -92,7 +97,7 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
         os.makedirs(output_dir, exist_ok=True)
         if "segm" in results:
             with open(os.path.join(output_dir, "metrics.json"), "w") as fh:
-                json.dump(results["segm"], fh)
+                json.dump({k: results[k] for k in ("segm", "boundary")} if boundary else results["segm"], fh)
     line = {"rank": rank, "videos": nvid, "frames": nfr, "windows": nwin, "wall_s": round(wall, 4),
             "videos_per_s": round(nvid / wall, 4) if wall > 0 else None,
             "frames_per_s": round(nfr / wall, 3) if wall > 0 else None,
@@ -115,7 +120,8 @@ def main(argv=None):
     model = build_model(cfg, a.weights or cfg.MODEL.WEIGHTS, device)
     with open(a.gt) as fh:
         gt_doc = json.load(fh)
-    results, line = evaluate_model(cfg, model, gt_doc, a.image_root, a.output_dir, device, a.threads, a.prefetch)
+    results, line = evaluate_model(cfg, model, gt_doc, a.image_root, a.output_dir, device, a.threads, a.prefetch,
+                                   boundary=a.boundary_ap, dilation_ratio=a.dilation_ratio)
     print(json.dumps(line), flush=True)
     if dist.is_initialized():
         dist.barrier()

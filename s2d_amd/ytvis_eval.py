@@ -11,7 +11,15 @@ truth, and the scores, categories and mean areas of its detections.
 The greedy matching, `accumulate` and `summarize` run on the host in numpy (per video O(10 D G); the accumulate sort is over all
 detections) with the reference's float operations, sort kinds and -1 sentinels, so `stats` come out identical.
 
-    python -m s2d_amd.ytvis_eval --gt ann.json --results results.json [--use-cats]
+Boundary AP (opt-in: iou_type="boundary" / boundary=True) scores contour quality, which mask IoU is nearly blind to on large
+objects: Cheng et al., "Boundary IoU" (CVPR 2021) and the published mask_to_boundary routine, restated.  A mask's boundary band
+is Bd = M & ~E, E = M eroded d times by a 3 x 3 square with everything outside the image counting as 0 (so mask pixels
+within d of the image edge are boundary), d = max(1, round(dilation_ratio * sqrt(H^2 + W^2))) (csrc/mask_boundary.hip).  A
+pair's video boundary IoU is  sum_t |Bd(d_t) & Bd(g_t)| / sum_t |Bd(d_t) | Bd(g_t)|,  the rule of the video mask IoU on the
+bands and exact from the same three integer quantities; the IoU that enters matching is min(mask IoU, boundary IoU), and areas
+stay mask areas.  The video form and the min rule are restated from the paper, not pinned against the boundary_iou package.
+
+    python -m s2d_amd.ytvis_eval --gt ann.json --results results.json [--use-cats] [--iou-type boundary] [--dilation-ratio 0.02]
 """
 import argparse
 import itertools
@@ -154,9 +162,33 @@ def cross_counts(a, b):
     return inter
 
 
-def video_ious(dt_bits, D, gt_bits, G, T):
-    """bit planes of D detection and G ground-truth tracks ([D*T, wpf], [G*T, wpf], frames of a track adjacent) ->
-    (ious float64 [D, G], detection frame areas int64 [D, T]).  iou = i / u in float64 from exact integer sums, 0 if u == 0."""
+def boundary_dilation(H, W, ratio=0.02):
+    """the erosion count of mask_to_boundary for an H x W image: max(1, round(ratio * image diagonal)), Python's round"""
+    return max(1, int(round(ratio * np.sqrt(H * H + W * W))))
+
+
+def boundary_planes(bits, H, W, d):
+    """int32 CUDA bit planes [F, ceil(H*W/32)] -> their boundary bands M & ~erode(M, d) in the same layout, padding bits 0
+    (s2d_mask_boundary_bits_u32)"""
+    import torch
+    from . import ops
+    from ._lib import lib
+    ops._chk(bits, torch.int32)
+    F, words = bits.shape
+    if words != (H * W + 31) // 32:
+        raise ValueError(f"planes of {words} words for a {H}x{W} image")
+    out = torch.empty_like(bits)
+    if F:
+        n = lib().call("s2d_mask_boundary_workspace_words", F, H, W, d)
+        if n < 0:
+            raise ValueError(f"boundary planes: F={F}, H={H}, W={W}, d={d} refused")
+        ws = torch.empty((n,), device=bits.device, dtype=torch.int32) if n else None
+        lib().call("s2d_mask_boundary_bits_u32", bits, F, H, W, d, ws, n, out, ops._stream())
+    return out
+
+
+def _track_ious(dt_bits, D, gt_bits, G, T):
+    """-> (ious float64 [D, G], frame areas int64 [D, T]) from the planes' integer sums"""
     wpf = dt_bits.shape[1] if D else gt_bits.shape[1]
     d_area = plane_areas(dt_bits) if D else None
     g_area = plane_areas(gt_bits) if G else None
@@ -171,6 +203,23 @@ def video_ious(dt_bits, D, gt_bits, G, T):
     pos = u > 0
     ious[pos] = i[pos] / u[pos]
     return ious, da
+
+
+def video_ious(dt_bits, D, gt_bits, G, T, boundary_d=None, size=None):
+    """bit planes of D detection and G ground-truth tracks ([D*T, wpf], [G*T, wpf], frames of a track adjacent) ->
+    (ious float64 [D, G], detection frame areas int64 [D, T]).  iou = i / u in float64 from exact integer sums, 0 if u == 0.
+    boundary_d (with size = (H, W)): -> (ious, areas, boundary ious float64 [D, G]), the same quotient on the planes'
+    boundary bands at dilation boundary_d; the areas stay those of the masks."""
+    ious, da = _track_ious(dt_bits, D, gt_bits, G, T)
+    if boundary_d is None:
+        return ious, da
+    if size is None:
+        raise ValueError("boundary_d needs size=(H, W)")
+    if not (D and G):
+        return ious, da, np.zeros((D, G))
+    H, W = size
+    bious, _ = _track_ious(boundary_planes(dt_bits, H, W, boundary_d), D, boundary_planes(gt_bits, H, W, boundary_d), G, T)
+    return ious, da, bious
 
 
 # --------------------------------------------------------------------------------------------------------------- data
@@ -381,8 +430,9 @@ def derive_results(stats):
     return {m: float(stats[i] * 100 if stats[i] >= 0 else "nan") for i, m in enumerate(METRICS) if i < len(stats)}
 
 
-def _video_record(gt, vid, dt_bits, D, T, H, W, device):
-    """IoU of D detection tracks (bit planes [D*T, wpf]) against the video's ground truth; -> (ious [D, G], frame areas [D, T])"""
+def _video_record(gt, vid, dt_bits, D, T, H, W, device, dilation_ratio=None):
+    """IoU of D detection tracks (bit planes [D*T, wpf]) against the video's ground truth; -> (ious [D, G], frame areas [D, T]),
+    and with a dilation_ratio (Boundary AP) the boundary IoUs [D, G] as a third item: the video is decoded once for both"""
     v = gt.video(vid)
     if (v["height"], v["width"]) != (H, W):
         raise ValueError(f"video {vid} is {v['height']}x{v['width']}, its predictions {H}x{W}")
@@ -390,16 +440,24 @@ def _video_record(gt, vid, dt_bits, D, T, H, W, device):
     if G and D and Tg != T:
         raise ValueError(f"video {vid}: predictions of {T} frames, ground truth of {Tg}")
     if D == 0:
-        return np.zeros((0, G)), np.zeros((0, T), np.int64)
-    if G == 0:
-        return np.zeros((D, 0)), plane_areas(dt_bits).cpu().numpy().astype(np.int64).reshape(D, T)
-    return video_ious(dt_bits, D, gt_bits, G, T)
+        rec = np.zeros((0, G)), np.zeros((0, T), np.int64)
+    elif G == 0:
+        rec = np.zeros((D, 0)), plane_areas(dt_bits).cpu().numpy().astype(np.int64).reshape(D, T)
+    elif dilation_ratio is None:
+        return video_ious(dt_bits, D, gt_bits, G, T)
+    else:
+        return video_ious(dt_bits, D, gt_bits, G, T, boundary_d=boundary_dilation(H, W, dilation_ratio), size=(H, W))
+    return rec if dilation_ratio is None else rec + (np.zeros((D, G)),)
 
 
-def evaluate_ytvis(gt, results, *, use_cats=False, max_dets=(1, 10, 100), device=None):
+def evaluate_ytvis(gt, results, *, use_cats=False, max_dets=(1, 10, 100), device=None, iou_type="segm", dilation_ratio=0.02):
     """Score an existing results list / results.json (what YTVISEvaluator writes, the reference's included) against a YTVIS
     annotation document / file, as _evaluate_predictions_on_coco does (useCats = 0 by default).  Returns the YTVISEval after
-    evaluate + accumulate (call .summarize() for the table and .stats).  Detection ids are result positions + 1 (loadRes)."""
+    evaluate + accumulate (call .summarize() for the table and .stats).  Detection ids are result positions + 1 (loadRes).
+    iou_type="boundary": Boundary AP -- matching on min(mask IoU, boundary IoU) at dilation_ratio, all else as for "segm"."""
+    if iou_type not in ("segm", "boundary"):
+        raise ValueError(f"iou_type {iou_type!r}: 'segm' or 'boundary'")
+    ratio = dilation_ratio if iou_type == "boundary" else None
     if isinstance(results, str):
         with open(results) as fh:
             results = json.load(fh)
@@ -416,7 +474,9 @@ def evaluate_ytvis(gt, results, *, use_cats=False, max_dets=(1, 10, 100), device
         tracks = [results[n]["segmentations"] for n in idx]
         T = _common_length(tracks, vid)
         bits = decode_frames([s for t in tracks for s in t], H, W, device)
-        ious, fa = _video_record(gt, vid, bits, len(idx), T, H, W, device)
+        ious, fa, *bious = _video_record(gt, vid, bits, len(idx), T, H, W, device, ratio)
+        if bious:
+            ious = np.minimum(ious, bious[0])
         areas = [[int(fa[d, t]) if tracks[d][t] else None for t in range(T)] for d in range(len(idx))]   # loadRes areas
         videos[vid] = {"dt_ids": [n + 1 for n in idx], "scores": [results[n]["score"] for n in idx],
                        "labels": [results[n]["category_id"] for n in idx], "avg_areas": [mean_area(a) for a in areas], "ious": ious}
@@ -428,10 +488,13 @@ class YTVISEvaluator:
     as train_net_video.py:87 builds it.  `dataset_name` resolves to MetadataCatalog.get(name).json_file when detectron2 is
     importable; otherwise pass `json_file=` (a path or a loaded document).  `process` scores one video on the device at once
     and keeps only its IoU matrix and detection scores / categories / areas (plus its RLE when `output_dir` is set, for the
-    results.json that evaluate() writes)."""
+    results.json that evaluate() writes).  boundary=True: Boundary AP as well -- `process` keeps the video's boundary IoU matrix
+    beside the mask one (one decode for both), evaluate() returns {"segm", "boundary"} and keeps `ytvis_eval_boundary`."""
 
-    def __init__(self, dataset_name=None, tasks=None, distributed=True, output_dir=None, *, json_file=None, dataset_id_to_contiguous_id=None):
+    def __init__(self, dataset_name=None, tasks=None, distributed=True, output_dir=None, *, json_file=None, dataset_id_to_contiguous_id=None,
+                 boundary=False, dilation_ratio=0.02):
         self._distributed, self._output_dir, self._tasks = distributed, output_dir, tasks
+        self._dilation_ratio = dilation_ratio if boundary else None
         if json_file is None:
             if dataset_name is None:
                 raise ValueError("YTVISEvaluator needs a dataset_name (with detectron2) or json_file=")
@@ -512,10 +575,13 @@ class YTVISEvaluator:
             if vid not in self._gt.videos:
                 raise ValueError(f"video {vid} is not in the ground truth")
             if D:
-                ious, fa = _video_record(self._gt, vid, bits, D, T, H, W, dev)
+                ious, fa, *bious = _video_record(self._gt, vid, bits, D, T, H, W, dev, self._dilation_ratio)
             else:
                 ious, fa = np.zeros((0, len(self._gt.anns.get(vid, [])))), np.zeros((0, 0), np.int64)
+                bious = [ious] if self._dilation_ratio is not None else []
             rec["ious"] = ious
+            if bious:
+                rec["boundary_ious"] = bious[0]
             rec["avg_areas"] = [mean_area([int(fa[d, t]) if present[d][t] else None for t in range(fa.shape[1])]) for d in range(D)]
         self._records.append(rec)
 
@@ -549,10 +615,12 @@ class YTVISEvaluator:
         videos, nid = {}, 0
         for r in records:                                   # detection ids: positions in the gathered prediction list + 1
             D = len(r["scores"])
-            v = videos.setdefault(r["video_id"], {"dt_ids": [], "scores": [], "labels": [], "avg_areas": [], "ious": []})
+            v = videos.setdefault(r["video_id"], {"dt_ids": [], "scores": [], "labels": [], "avg_areas": [], "ious": [], "boundary_ious": []})
             v["dt_ids"] += list(range(nid + 1, nid + D + 1))
             v["scores"] += r["scores"]; v["labels"] += r["labels"]; v["avg_areas"] += r["avg_areas"]
             v["ious"].append(r["ious"])
+            if self._dilation_ratio is not None:
+                v["boundary_ious"].append(r["boundary_ious"])
             nid += D
         for v in videos.values():
             v["ious"] = np.concatenate(v["ious"], 0)
@@ -560,6 +628,12 @@ class YTVISEvaluator:
         ev.summarize()
         self.ytvis_eval = ev
         results["segm"] = derive_results(ev.stats)
+        if self._dilation_ratio is not None:                # Boundary AP: the same detections matched on min(mask, boundary) IoU
+            bvideos = {vid: dict(v, ious=np.minimum(v["ious"], np.concatenate(v["boundary_ious"], 0))) for vid, v in videos.items()}
+            evb = YTVISEval(self._gt, use_cats=False, max_dets=(1, 10, 100)).evaluate(bvideos).accumulate()
+            evb.summarize()
+            self.ytvis_eval_boundary = evb
+            results["boundary"] = derive_results(evb.stats)
         return results
 
 
@@ -568,8 +642,10 @@ def main(argv=None):
     ap.add_argument("--gt", required=True, help="YTVIS annotation JSON")
     ap.add_argument("--results", required=True, help="results.json (list of {video_id, score, category_id, segmentations})")
     ap.add_argument("--use-cats", action="store_true", help="per-category matching (the stock YTVIS protocol); default pools categories")
+    ap.add_argument("--iou-type", choices=("segm", "boundary"), default="segm", help="boundary: Boundary AP, matching on min(mask IoU, boundary IoU)")
+    ap.add_argument("--dilation-ratio", type=float, default=0.02, help="boundary band width as a fraction of the image diagonal (--iou-type boundary)")
     a = ap.parse_args(argv)
-    evaluate_ytvis(a.gt, a.results, use_cats=a.use_cats).summarize()
+    evaluate_ytvis(a.gt, a.results, use_cats=a.use_cats, iou_type=a.iou_type, dilation_ratio=a.dilation_ratio).summarize()
 
 
 if __name__ == "__main__":
