@@ -16,6 +16,13 @@
 // a lane owns one query column: the online-softmax max/sum are per-lane scalars, and the probabilities P
 // (the accumulator registers) are directly the B operand of O^T[d][q] += V^T . P^T -- no LDS round trip
 // for P and no cross-lane rescale.  Partial (O, m, l) per key split are merged by a second tiny kernel.
+//
+// tests/test_gpu_attn_masks.py pins, against float64, what the model's own masks and logits ask of these kernels: whole tiles, whole
+// forward / backward splits and trailing empty splits masked for a query (m = -1e30, l = 0 carried and dropped by the merges, exact-zero
+// dK / dV rows), K = 1 .. 129 against Q = 1 .. 128, scores up to |s| ~ 270 with a common-mode part, and fp16-subnormal probability
+// splits (profiles/attn_masks_parity.txt).  The MFMA backward recomputes the scores with the forward's own arithmetic, so s - lse is
+// consistent at any magnitude; the scalar pair (S2D_ATTN_BWD_MFMA=0) forms them with fp32 FMAs against the forward's lse and is held
+// to the bound at unit-scale scores only (at |s| ~ 270 its dQ is 1.8e-3 off).
 #include "split_f16.h"
 #include <stdlib.h>
 
