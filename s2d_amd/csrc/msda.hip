@@ -367,7 +367,9 @@ __global__ __launch_bounds__(TILED ? 1024 : 256) void msda_fused_kernel(const fl
 //   phase 1  lane (head m, j) prepares samples j and j + 8 of its head as in the SHARE form (same formulas, same order) and writes one
 //            RECORD per sample into the wave's own LDS area: the four corners' BYTE OFFSETS into the frame's value slice (0x80000000 for a
 //            corner outside the map: the buffer load's bounds check then returns zeros, which is the value the reference gives a missing
-//            corner, cuh:61-83), the four bilinear weights and the attention weight;
+//            corner, cuh:61-83), the four bilinear weights and the attention weight; a sample outside every map (range test false, which
+//            a NaN, infinite or huge offset also is) has all four offsets 0x80000000 AND all five weights 0, so it adds exactly +0 -- with
+//            the weights as computed, NaN or inf times the loaded zeros reached the accumulator (tests/test_gpu_msda_edges.py: nonfinite);
 //   phase 2  twelve branch-free steps: the 8 lanes of a head read their record (two ds_read_b128 + one ds_read_b32, broadcast within the
 //            head, conflict-free across heads), issue four buffer_load_dwordx4 with 32-bit offsets (no 64-bit address arithmetic) and
 //            accumulate; nothing in a step depends on the previous one but the accumulator, so the compiler keeps several samples' loads
@@ -447,7 +449,9 @@ void msda_fused_rec_kernel(const float *__restrict__ value, int ldv, Levels lv, 
             const bool in = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;   // cuh:293
             const int h0 = (int)floorf(h_im), w0 = (int)floorf(w_im), h1 = h0 + 1, w1 = w0 + 1;
             const float lh = h_im - h0, lw = w_im - w0, hh = 1.f - lh, hw = 1.f - lw;
-            const f32x4 cw = {hh * hw, hh * lw, lh * hw, lh * lw};
+            // a sample that fails the range test (a NaN / inf / huge offset included, whose lh, lw are NaN or inf) gets weight 0: the zeros
+            // its four corners load then add exactly nothing, as the reference skips it (cuh:293) and as the TILED / SHARE forms `continue`
+            const f32x4 cw = in ? f32x4{hh * hw, hh * lw, lh * hw, lh * lw} : f32x4(0.f);
             const bool t = in && h0 >= 0, b = in && h1 <= H - 1, lft = w0 >= 0, rgt = w1 <= W - 1;
             const unsigned int p00 = (unsigned int)(st + h0 * W + w0) * ldv4;  // wraps for h0 / w0 = -1; only used where the corner exists
             typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
@@ -456,7 +460,7 @@ void msda_fused_rec_kernel(const float *__restrict__ value, int ldv, Levels lv, 
             unsigned char *d = rec + i * REC_ROW + m * REC_HEAD;
             *reinterpret_cast<u32x4_t *>(d) = off;
             *reinterpret_cast<f32x4 *>(d + 16) = cw;
-            *reinterpret_cast<float *>(d + 32) = own_e[r] * inv;
+            *reinterpret_cast<float *>(d + 32) = in ? own_e[r] * inv : 0.f;
         }
     }
     // the records cross lanes inside the wave only: LDS instructions of one wave execute in order; keep the compiler from moving the
@@ -912,12 +916,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             smask[r] = !in ? 0 : ((h0 >= 0 && w0 >= 0) ? 1 : 0) | ((h0 >= 0 && w1 <= W - 1) ? 2 : 0) | ((h1 <= H - 1 && w0 >= 0) ? 4 : 0) |
                                  ((h1 <= H - 1 && w1 <= W - 1) ? 8 : 0);
             const int wx = w0 - gox[r], wy = h0 - goy[r];
-            const bool inw = wx >= 0 && wx + 1 < gww[r] && wy >= 0 && wy + 1 < gwh[r];
+            // a NaN, infinite or huge position has no meaningful floor (a NaN converts to 0, which may lie inside the window, with NaN
+            // weights): it never counts as inside a window, so no LDS index is formed from it and its wave takes the general path, which
+            // skips it (tests/test_gpu_msda_edges.py: the nonfinite row put NaN into the output without this)
+            const bool fin = fabsf(h_im) < 1e9f && fabsf(w_im) < 1e9f;
+            const bool inw = fin && wx >= 0 && wx + 1 < gww[r] && wy >= 0 && wy + 1 < gwh[r];
             swin[r] = inw ? (gbase[r] + wy * gww[r] + wx) * 8 + c : -1;      // float4 index of the upper left tap, this lane's channel column
         }
         // Branch-free form when every sample of the wave has its 2 x 2 footprint inside the windows.  A sample outside the map
         // (`in` false, skipped by the general path) then reads zeros (staged for pixels outside the map) or, at h_im == -1 /
-        // w_im == -1 exactly, map pixels under a weight of exactly 0: it adds +0 either way.
+        // w_im == -1 exactly, map pixels under a weight of exactly 0: it adds +0 either way (its position is finite: see `fin`).
         fast = __all((swin[0] >= 0) && (!live1 || swin[1] >= 0));
     };
     f32x4 acc;
