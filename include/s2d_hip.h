@@ -501,6 +501,32 @@ long s2d_mask_boundary_workspace_words(int F, int H, int W, int d);
 int s2d_mask_boundary_bits_u32(const uint32_t *bits, int F, int H, int W, int d, uint32_t *workspace, long workspace_words,
                                uint32_t *out, hipStream_t stream);
 
+/* ---- DAVIS J&F evaluation (s2d_amd/davis_eval.py, csrc/davis_eval.hip; the davis2017 evaluation code restated, toolkit parity
+ * unpinned).  All planes are in the flat layout above: [..][ceil(H*W/32)], pixel i -> word i/32, bit i%32, rows not word-aligned
+ * unless W % 32 == 0; padding bits of a plane's last word are ignored on input and written 0. ------------------------------------ */
+
+/* index u8 [T][H][W] (a DAVIS index PNG per frame) -> planes [K][T][wpf], plane k-1 = (index == k) for the labels 1..K, and
+ * void_plane [T][wpf] = (index == 255).  Labels K+1..254 (and 0) set no bit.  0 <= K <= 254 (planes may be null for K = 0).  Every
+ * output word is stored once: no zero fill is needed. */
+int s2d_index_planes_u32(const uint8_t *index, int T, int H, int W, int K, uint32_t *planes, uint32_t *void_plane, hipStream_t stream);
+
+/* seg2bmap without resize: out = (M != E) | (M != S) | (M != SE) for F planes, E / S / SE the east, south and south-east
+ * neighbours with the image edge replicated (the last row compares only east, the last column only south, the bottom-right pixel
+ * is 0).  out may not alias bits. */
+int s2d_seg2bmap_bits_u32(const uint32_t *bits, int F, int H, int W, uint32_t *out, hipStream_t stream);
+
+/* out = the F planes dilated by the disk {(dx, dy): dx^2 + dy^2 <= R^2}, pixels outside the image counting as 0; any H, W >= 1
+ * with H*W < 2^31 (a disk larger than the image included), 1 <= R <= 64 in one pass; R > 64 returns S2D_ERR_ARG (disks do not
+ * compose exactly on the lattice, so there is no chaining).  F times the tiles of a plane must stay below 2^31.  out may not alias
+ * bits; bitwise deterministic. */
+int s2d_disk_dilate_bits_u32(const uint32_t *bits, int F, int H, int W, int R, uint32_t *out, hipStream_t stream);
+
+/* out [P][G][T] int32 = popcount(a[p][t] & b[g][t]) per frame, for a [P][T][words_per_frame] and b [G][T][words_per_frame]; zeroed
+ * by the call.  T < 65536, words_per_frame < 2^26 (a plane of fewer than 2^31 pixels: every count fits).  The per-frame
+ * companion of s2d_mask_cross_counts_u64, which sums whole tracks. */
+int s2d_mask_frame_cross_counts_i32(const uint32_t *a, int P, const uint32_t *b, int G, int T, long words_per_frame, int *out,
+                                    hipStream_t stream);
+
 /* ---- test-time frame resize (s2d_amd/data/resize.py, data/test_loader.py): detectron2 ResizeTransform.apply_image =
  * PIL Image.resize(BILINEAR) on uint8 RGB frames, bit-exact ------------------------------------------------------------- */
 
