@@ -90,6 +90,9 @@ int s2d_conv2d_nhwc_gate_f32(const float *x, const float *w, float *y, int N, in
 int s2d_gemm_nt_presplit_f32(const void *A_split, const float *B, float *C, int M, int N, int K, long ldb, long ldc, const float *bias,
                              const float *res, long ldr, int res_rows, int res_cols, int relu, const void *B_split, hipStream_t stream);
 long s2d_split_weights_words(int N, int K);
+/* launches of s2d_gemm_nt_f32 that the row-resident short-K kernel has taken so far in this process (S2D_GEMM_ROWS: 0 never,
+ * 1 = default by a measured shape rule, 2 every launch the kernel accepts); the results do not depend on the setting */
+long s2d_gemm_rows_launches(void);
 int s2d_split_weights_f16(const float *W, int N, int K, long ldw, void *out, hipStream_t stream);
 
 /* The encoder layer's feed-forward block in one launch (split-fp16 x3 arithmetic, dense mode 2's):

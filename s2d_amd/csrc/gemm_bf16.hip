@@ -2027,6 +2027,20 @@ int s2d_split_weights_launch(const float *W, int N, int K, long ldw, unsigned in
     return S2D_OK;
 }
 
+// Where the row-resident kernel (gemm_rows.hip) is taken by default: the shape classes in which it measured >= 5 % faster than the tiled
+// kernels in isolation (scripts/mb_gemm_rows.py, profiles/gemm_rows/per_shape.txt; time tiled / time row-resident):
+//   58 880 x 1024 x 256  1.48     235 520 x 768 x 256  1.17     309 120 x 544 x 256  1.21     235 520 x 512 x 128  1.11     942 080 x 256 x 256  1.08
+//   942 080 x 256 x 64   0.97     942 080 x 128 x 256  0.94      58 880 x 768 x 256  1.00      14 720 x 768 x 256  0.56
+// What it saves per row is the re-load and re-split of K values for every 64-column tile after the first, ~ N . K: the winners have
+// N . K >= 64 K values, the two large-M losers 16 K and 32 K.  It launches M / 128 workgroups that run two to a CU and have a
+// serial prologue each (load, split, first weight stage), so it needs M >= 64 K rows = two full rounds of the chip; below that only
+// the widest output still wins (58 880 rows: N = 1024 yes, N = 768 a tie), and at 115 workgroups it loses to the tiled kernels' 1 380.
+static bool gemm_rows_wins(const GemmParams &p)
+{
+    if (p.M >= 65536) return (long)p.N * p.K >= 65536;
+    return p.M >= 32768 && p.N >= 1024 && p.K >= 256;
+}
+
 int s2d_launch_gemm_bf16x3(const GemmParams &pin, bool conv, int batch, hipStream_t st, int f16)
 {
     GemmParams p = pin;
@@ -2039,6 +2053,10 @@ int s2d_launch_gemm_bf16x3(const GemmParams &pin, bool conv, int batch, hipStrea
         p.kblocks = (p.K + 31) / 32;
     }
     if (!f16 && (p.Asplit || p.gate || p.drop_thresh)) return S2D_ERR_ARG;
+    // row-resident kernel (gemm_rows.hip; S2D_GEMM_ROWS, read per call: 0 never, 2 every launch it takes, 1 = default: by the rule below)
+    int rows = 1;
+    if (const char *e = getenv("S2D_GEMM_ROWS")) rows = atoi(e);
+    if (rows && s2d_gemm_rows_ok(p, conv, batch, f16) && (rows == 2 || gemm_rows_wins(p))) return s2d_launch_gemm_rows(p, st);
     if (s2d_gemm_small_m_ok(p, conv, batch, f16)) return s2d_launch_gemm_small_m(p, st);      // the video decoder's query side (M = 200)
     static int ws = -1;
     if (ws < 0) { const char *e = getenv("S2D_GEMM_WS"); ws = e ? atoi(e) : 0; }

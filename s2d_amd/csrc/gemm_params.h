@@ -44,3 +44,6 @@ int s2d_launch_gemm_bf16x3(const GemmParams &p, bool conv, int batch, hipStream_
 // gemm_small.hip: one-round-trip kernel for launches of a handful of rows (M <= 256) against static pre-split weights
 bool s2d_gemm_small_m_ok(const GemmParams &p, bool conv, int batch, int f16);
 int s2d_launch_gemm_small_m(const GemmParams &p, hipStream_t st);
+// gemm_rows.hip: short K (<= 256) against static pre-split weights, a workgroup keeps its split rows resident and walks the column tiles
+bool s2d_gemm_rows_ok(const GemmParams &p, bool conv, int batch, int f16);
+int s2d_launch_gemm_rows(const GemmParams &p, hipStream_t st);
