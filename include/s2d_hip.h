@@ -530,6 +530,58 @@ int s2d_disk_dilate_bits_u32(const uint32_t *bits, int F, int H, int W, int R, u
 int s2d_mask_frame_cross_counts_i32(const uint32_t *a, int P, const uint32_t *b, int G, int T, long words_per_frame, int *out,
                                     hipStream_t stream);
 
+/* ---- COCO image evaluation (s2d_amd/coco_eval.py, csrc/coco_eval.hip; COCOeval.computeIoU / evaluateImg and maskApi.c bbIou
+ * restated, pycocotools parity unpinned).  Every call handles a CHUNK of N images of different sizes in one launch.
+ *
+ * Ragged layout.  The detections of the chunk are numbered flat, image after image (result order inside an image); so are the
+ * ground truths (document order).  Per-detection arrays (area_d, dt_box [.][4], dt_area) and per-ground-truth arrays (area_g,
+ * gt_box [.][4], gt_area, crowd, gt_ignore) are indexed by these flat numbers.  The pairs of an image are a row-major [D][G]
+ * block; the blocks lie back to back in `inter` / `iou`.  img is a DEVICE int64 table [N][9], one row per image:
+ *   0 dt_word  first word of the image's D detection planes in `bits` (planes back to back, `wpp` words each)
+ *   1 gt_word  first word of its G ground-truth planes
+ *   2 wpp      words per plane, ceil(H*W / 32): the plane layout of s2d_rle_decode_bits
+ *   3 hw       H*W (< 2^31)
+ *   4 D        5 G
+ *   6 dt0      flat number of the image's first detection        7 gt0  of its first ground truth
+ *   8 pair0    offset of its [D][G] block in `inter` / `iou`  (= sum of D*G of the images before it)
+ * Columns 0-3 are read by the mask kernel only. ------------------------------------------------------------------------------- */
+
+/* Mask IoU of every (detection, ground truth) pair of the chunk.  bits: all planes, placed as img says.  tiles: DEVICE int32
+ * [n_tiles][3] = {image, ti, tj}: the 8 x 8 pair tile (detections 8*ti.., ground truths 8*tj..) one workgroup computes; the host
+ * lists max(1, ceil(D/8)) * max(1, ceil(G/8)) tiles for every image with D + G > 0 (an image with only one kind still gets its
+ * areas), each exactly once.  Outputs: inter[pair] = |d & g| (exact), area_d / area_g = pixels per plane, iou[pair] =
+ * (double)i / (double)u with u = area_d + area_g - i, or u = area_d where crowd[g] != 0, and 0 where u == 0.  Bits of a plane's
+ * last word at and beyond H*W are not counted.  Every output element is stored exactly once: no zero fill, no atomics, bitwise
+ * deterministic. */
+int s2d_coco_mask_iou_ragged(const uint32_t *bits, const long *img, int N, const int *tiles, int n_tiles, const uint8_t *crowd,
+                             long long *inter, int *area_d, int *area_g, double *iou, hipStream_t stream);
+
+/* Box IoU of every pair of the chunk, boxes [x, y, w, h] float64, in bbIou's operation order: w = min(x1+w1, x2+w2) - max(x1, x2),
+ * h likewise; a pair with w <= 0 or h <= 0 is 0 (the clamp; no division); else i = w*h, u = crowd ? a_d : a_d + a_g - i with
+ * a = w*h of each box, iou = i / u.  pair_off: DEVICE int64 [N+1] = pair0 of every image and the total n_pairs. */
+int s2d_coco_box_iou_ragged(const double *dt_box, const double *gt_box, const uint8_t *crowd, const long *img, int N,
+                            const long *pair_off, long n_pairs, double *iou, hipStream_t stream);
+
+/* COCOeval.evaluateImg for n_groups groups x A area ranges x T thresholds in one launch.  A group is an image (or an image and a
+ * category): groups is a DEVICE int64 table [n_groups][8] = {pair0, G_image (row stride of the image's IoU block), dt0, gt0,
+ * dsel0, D, gsel0, G}; dsel[dsel0 .. +D) are the group's detections (flat numbers) in descending score order, already cut at
+ * maxDets[-1]; gsel[gsel0 .. +G) its ground truths (flat numbers) in document order; dsel0 / gsel0 are the exclusive prefix sums
+ * of D / G over the groups.  iou_thrs [T] and area_rng [A][2] are float64 DEVICE arrays, used as given.  Per problem (group, a):
+ * the ground truths are stably sorted with the ignored ones last (ignored: gt_ignore != 0, or gt_area outside [lo, hi]); for each
+ * threshold the detections are scanned in order, each over the sorted ground truths: a taken non-crowd one is skipped, the scan
+ * stops at the first ignored one once a regular one is matched, iou < best is skipped (equal: the later wins; iou == t matches),
+ * best starts at min(t, 1 - 1e-10).  An unmatched detection with dt_area outside the range is ignored.
+ * Outputs (int32), with gb = A*gsel0 + a*G and db = A*dsel0 + a*D:
+ *   gt_perm[gb + k]            position in gsel of the k-th sorted ground truth      gt_ignore_out[gb + k]  its ignore flag
+ *   gt_match[T*gb + t*G + k]   position in dsel of the detection matched to it at threshold t, -1 if none
+ *   dt_match[T*db + t*D + d]   sorted position k of the ground truth matched to detection d, -1 if none
+ *   dt_ignore[T*db + t*D + d]  1 if the match is an ignored ground truth, or unmatched and out of range
+ * Every element is stored; no inter-workgroup communication; all loop bounds are table entries. */
+int s2d_coco_match(const double *iou, const long *groups, int n_groups, const int *dsel, const int *gsel, const double *dt_area,
+                   const double *gt_area, const uint8_t *gt_ignore, const uint8_t *crowd, const double *iou_thrs, int T,
+                   const double *area_rng, int A, int *dt_match, int *gt_match, int *dt_ignore, int *gt_ignore_out, int *gt_perm,
+                   hipStream_t stream);
+
 /* ---- test-time frame resize (s2d_amd/data/resize.py, data/test_loader.py): detectron2 ResizeTransform.apply_image =
  * PIL Image.resize(BILINEAR) on uint8 RGB frames, bit-exact ------------------------------------------------------------- */
 

@@ -11,7 +11,13 @@ OUT/metrics.json (the "segm" dict; with --boundary-ap {"segm": ..., "boundary": 
 pass over the videos; not for a split without annotations) and prints one JSON timing line: videos/s, frames/s, the
 number of windows run (one per video unless MODEL.MASK_FORMER.TEST.WINDOW_INFERENCE cuts long videos) and the fraction of the wall
 time the model waited on the loader.  Under torch.distributed.run the videos are split round-robin by
-rank and rank 0 writes the files."""
+rank and rank 0 writes the files.
+
+--test-format auto|ytvis|coco_image (auto: a --gt document with `images` and no `videos` is a COCO image file,
+data/image_clip.detect_train_format): a COCO instances document is scored image by image -- every image a one-frame video through
+the same `model([inputs])` (data/coco_image_loader.COCOImageTestLoader, coco_eval.COCOImageEvaluator) -- and the run writes
+OUT/coco_instances_results.json and OUT/metrics.json as {"segm": ..., "bbox": ...} (mask AP and box AP of the masks' tight boxes,
+12 metrics each); the timing line counts `images`.  --boundary-ap is a YTVIS option: with the image format it is refused."""
 import argparse
 import json
 import os
@@ -33,6 +39,8 @@ def parse_args(argv=None):
     ap.add_argument("--dist-backend", default="gloo", help="process group backend under torch.distributed.run")
     ap.add_argument("--boundary-ap", action="store_true", help="also score Boundary AP (matching on min(mask IoU, boundary IoU))")
     ap.add_argument("--dilation-ratio", type=float, default=0.02, help="boundary band width as a fraction of the image diagonal")
+    ap.add_argument("--test-format", choices=("auto", "ytvis", "coco_image"), default="auto",
+                    help="the --gt document: YTVIS videos or COCO images (auto: `images` without `videos` is coco_image)")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="config overrides KEY VALUE ...")
     return ap.parse_args(argv)
 
@@ -53,10 +61,24 @@ def build_model(cfg, weights, device):
     return model
 
 
-def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, prefetch=2, boundary=False, dilation_ratio=0.02):
+def resolve_test_format(fmt, doc, boundary=False):
+    """--test-format -> "ytvis" or "coco_image" for the loaded --gt document; --boundary-ap with the image format is refused"""
+    from .data.image_clip import detect_train_format
+    if fmt not in ("auto", "ytvis", "coco_image"):
+        raise ValueError(f"test format {fmt!r}: auto, ytvis or coco_image")
+    fmt = detect_train_format(doc) if fmt == "auto" else fmt
+    if fmt == "coco_image" and boundary:
+        raise ValueError("--boundary-ap scores YTVIS videos: it is not available with --test-format coco_image")
+    return fmt
+
+
+def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, prefetch=2, boundary=False, dilation_ratio=0.02,
+                   test_format="ytvis"):
     """score `model` on a YTVIS split: every video through `model([inputs])` (eval mode, predictions as COCO RLE) with the test
     loader and YTVISEvaluator; writes output_dir/results.json and, on rank 0 of a split with annotations, output_dir/metrics.json
     (boundary: Boundary AP as well, and metrics.json holds {"segm", "boundary"}).
+    test_format "coco_image" ("auto": decided by the document): a COCO image split instead -- COCOImageTestLoader and
+    COCOImageEvaluator, files output_dir/coco_instances_results.json and metrics.json = {"segm", "bbox"}, `images` in the timing line.
     The model's training mode and inference_rle switch are restored afterwards.  -> (results, timing line dict)"""
     from .data.test_loader import YTVISTestLoader
     from .ytvis_eval import YTVISEvaluator
@@ -67,10 +89,17 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
             gt = json.load(fh)
     # labels -> dataset category ids as the registered dataset's metadata maps them (load_ytvis_json: sorted ids, contiguous)
     id_map = {c: i for i, c in enumerate(sorted(c["id"] for c in gt.get("categories", [])))} or None
-    evaluator = YTVISEvaluator(json_file=gt, distributed=True, output_dir=output_dir, dataset_id_to_contiguous_id=id_map,
-                               boundary=boundary, dilation_ratio=dilation_ratio)
+    images = resolve_test_format(test_format, gt, boundary) == "coco_image"
+    if images:
+        from .coco_eval import COCOImageEvaluator
+        from .data.coco_image_loader import COCOImageTestLoader
+        evaluator = COCOImageEvaluator(json_file=gt, distributed=True, output_dir=output_dir, dataset_id_to_contiguous_id=id_map)
+        loader = COCOImageTestLoader.from_config(cfg, gt, image_root, device=device, threads=threads, prefetch=prefetch)
+    else:
+        evaluator = YTVISEvaluator(json_file=gt, distributed=True, output_dir=output_dir, dataset_id_to_contiguous_id=id_map,
+                                   boundary=boundary, dilation_ratio=dilation_ratio)
+        loader = YTVISTestLoader.from_config(cfg, gt, image_root, device=device, threads=threads, prefetch=prefetch)
     evaluator.reset()
-    loader = YTVISTestLoader.from_config(cfg, gt, image_root, device=device, threads=threads, prefetch=prefetch)
 
     was_training, was_rle = model.training, getattr(model, "inference_rle", False)
     model.eval()
@@ -97,9 +126,10 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
         os.makedirs(output_dir, exist_ok=True)
         if "segm" in results:
             with open(os.path.join(output_dir, "metrics.json"), "w") as fh:
-                json.dump({k: results[k] for k in ("segm", "boundary")} if boundary else results["segm"], fh)
-    line = {"rank": rank, "videos": nvid, "frames": nfr, "windows": nwin, "wall_s": round(wall, 4),
-            "videos_per_s": round(nvid / wall, 4) if wall > 0 else None,
+                json.dump({k: results[k] for k in (("segm", "bbox") if images else ("segm", "boundary"))} if boundary or images
+                          else results["segm"], fh)
+    line = {"rank": rank, "images" if images else "videos": nvid, "frames": nfr, "windows": nwin, "wall_s": round(wall, 4),
+            "images_per_s" if images else "videos_per_s": round(nvid / wall, 4) if wall > 0 else None,
             "frames_per_s": round(nfr / wall, 3) if wall > 0 else None,
             "loader_wait_fraction": round(loader.wait_s / wall, 4) if wall > 0 else None}
     return results, line
@@ -117,11 +147,12 @@ def main(argv=None):
     torch.cuda.set_device(device)
 
     cfg = load_config(a.config_file, a.opts)
-    model = build_model(cfg, a.weights or cfg.MODEL.WEIGHTS, device)
     with open(a.gt) as fh:
         gt_doc = json.load(fh)
+    fmt = resolve_test_format(a.test_format, gt_doc, a.boundary_ap)
+    model = build_model(cfg, a.weights or cfg.MODEL.WEIGHTS, device)
     results, line = evaluate_model(cfg, model, gt_doc, a.image_root, a.output_dir, device, a.threads, a.prefetch,
-                                   boundary=a.boundary_ap, dilation_ratio=a.dilation_ratio)
+                                   boundary=a.boundary_ap, dilation_ratio=a.dilation_ratio, test_format=fmt)
     print(json.dumps(line), flush=True)
     if dist.is_initialized():
         dist.barrier()

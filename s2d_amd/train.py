@@ -25,7 +25,8 @@ when (iter + 1) % CHECKPOINT_PERIOD == 0, OUT/model_final.pth at MAX_ITER - 1, e
 continues at iteration + 1; with SEED < 0 it also reuses the saved sampler seed, so the resumed run draws the clips an
 uninterrupted run would (with SEED >= 0 the config's seed is used).
 With --eval-gt the model is scored (evaluate.evaluate_model) every TEST.EVAL_PERIOD iterations and after the last one, into
-OUT/inference/.
+OUT/inference/.  An --eval-gt document with `images` and no `videos` is scored as COCO images (coco_eval.COCOImageEvaluator: mask
+AP and box AP, OUT/inference/metrics.json = {"segm", "bbox"}); a YTVIS document as before.
 
 Not supported (refused): INPUT.DISENTANGLE_DISTILLATION_LOADER (the meta-archs take no distill_image) and optimizers other than
 ADAMW.  SOLVER.AMP.ENABLED is ignored with a message: the arithmetic is fp32-class, as in evaluate.py."""
@@ -58,7 +59,7 @@ def parse_args(argv=None):
     ap.add_argument("--output-dir", required=True)
     ap.add_argument("--weights", default=None, help="initial weights, torch .pth or detectron2 .pkl (default: MODEL.WEIGHTS)")
     ap.add_argument("--resume", action="store_true", help="continue from OUTPUT_DIR/last_checkpoint")
-    ap.add_argument("--eval-gt", default=None, help="YTVIS annotation JSON to score on (EvalHook)")
+    ap.add_argument("--eval-gt", default=None, help="YTVIS or COCO image annotation JSON to score on (EvalHook)")
     ap.add_argument("--eval-image-root", default=None)
     ap.add_argument("--threads", type=int, default=8, help="JPEG decode threads (<= 16)")
     ap.add_argument("--prefetch", type=int, default=2, help="batches prepared ahead")
@@ -245,9 +246,9 @@ def main(argv=None):
     def run_eval():
         if a.eval_gt:
             out = os.path.join(a.output_dir, "inference")
-            results, line = evaluate_model(cfg, model, a.eval_gt, a.eval_image_root, out, device, a.threads)
+            results, line = evaluate_model(cfg, model, a.eval_gt, a.eval_image_root, out, device, a.threads, test_format="auto")
             if rank == 0:
-                print(json.dumps({"eval_iteration": it, **line, **({"segm": results["segm"]} if "segm" in results else {})}),
+                print(json.dumps({"eval_iteration": it, **line, **{k: results[k] for k in ("segm", "bbox") if k in results}}),
                       flush=True)
 
     hist, names = [], None
