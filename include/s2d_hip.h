@@ -504,6 +504,39 @@ long s2d_mask_boundary_workspace_words(int F, int H, int W, int d);
 int s2d_mask_boundary_bits_u32(const uint32_t *bits, int F, int H, int W, int d, uint32_t *workspace, long workspace_words,
                                uint32_t *out, hipStream_t stream);
 
+/* The same band for a CHUNK of N images of different sizes in one launch (the COCO image evaluator: the planes of a chunk lie
+ * in one flat buffer, and `out` is read by s2d_coco_mask_iou_ragged through the same img / tiles tables as `bits`).
+ *
+ * s2d_mask_boundary_ragged_plan is pure host code: it touches no device and runs on a machine without one.  spec is a HOST
+ * int64 table [N][5] = {word0, F, H, W, d}: image n has F >= 0 planes of wpp = ceil(H*W/32) words, back to back from word
+ * word0 of `bits`, and at the same offsets of `out` (COCO chunk layout: word0 = the image's dt_word, F = D + G).  It writes the
+ * HOST int64 table plan [N][12], one row per image:
+ *   0 word0   1 F   2 H   3 W      as given
+ *   4 d       clamped to (min(H, W) + 1) / 2 (a window that does not fit leaves E empty: out = the mask)
+ *   5 wpp     ceil(H*W / 32)
+ *   6 S       row-aligned words per row, ceil(W / 32)
+ *   7 TW      words per tile row: S cut evenly into ntx = ceil(S / 32) word tiles
+ *   8 TR      rows per tile: H cut evenly into nty = ceil(H / (8192 / TW - 2d)) row bands
+ *   9 ntx    10 nty
+ *  11 wg0     the image's first workgroup: the exclusive prefix sum of F * ntx * nty
+ * and *n_workgroups = the sum of F * ntx * nty, *lds_bytes = the largest 2 * TW * (TR + 2d) * 4 of any image that has planes
+ * (0 if none has).  N == 0 and images with F == 0 are valid.  Returns S2D_ERR_ARG, with nothing written, for: H < 1, W < 1,
+ * H*W >= 2^31, d < 1, F < 0; a clamped d above 64 (the ragged call is one pass: such an image goes through
+ * s2d_mask_boundary_bits_u32, which chains passes); planes that leave [0, total_words); images whose word ranges overlap or
+ * do not ascend; n_workgroups >= 2^31; lds_bytes > 65536.
+ *
+ * s2d_mask_boundary_ragged_u32 derives every plan row again from the first five columns of plan_host and refuses
+ * (S2D_ERR_ARG, nothing launched, `out` untouched) a table that is not what the plan call writes; it also refuses a null
+ * bits / out / plan_host / plan_dev and out == bits.  plan_dev is the caller's DEVICE copy of plan_host.  ONE kernel launch
+ * for the whole chunk (none if no image has planes); when an image with planes has W % 32 != 0, one zero fill of
+ * out[0 .. total_words) comes first.  Per plane the semantics are those of s2d_mask_boundary_bits_u32: padding bits are ignored
+ * on input and written 0; bitwise deterministic.  Words of `out` that belong to no plane (gaps between images, the ranges of
+ * images listed with F == 0 planes) are written 0 when the zero fill runs and are left alone otherwise: a caller that keeps
+ * something there writes it after the call. */
+int s2d_mask_boundary_ragged_plan(const long *spec, int N, long total_words, long *plan, long *n_workgroups, long *lds_bytes);
+int s2d_mask_boundary_ragged_u32(const uint32_t *bits, long total_words, const long *plan_host, const long *plan_dev, int N,
+                                 uint32_t *out, hipStream_t stream);
+
 /* ---- DAVIS J&F evaluation (s2d_amd/davis_eval.py, csrc/davis_eval.hip; the davis2017 evaluation code restated, toolkit parity
  * unpinned).  All planes are in the flat layout above: [..][ceil(H*W/32)], pixel i -> word i/32, bit i%32, rows not word-aligned
  * unless W % 32 == 0; padding bits of a plane's last word are ignored on input and written 0. ------------------------------------ */

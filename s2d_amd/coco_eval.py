@@ -21,7 +21,17 @@ given, else the tight box of its mask.  Area ranges: all [0, 1e10], small [0, 32
 Detection ids are result positions + 1 (loadRes).  Refused: results for an image the ground truth does not have; an RLE whose size
 is not the image's; a "segm" result or annotation without a segmentation; a "bbox" one with neither `bbox` nor segmentation.
 
-    python -m s2d_amd.coco_eval --gt ann.json --results res.json [--iou-type segm|bbox] [--use-cats]
+Boundary AP (opt-in: iou_type="boundary") scores contour quality, which mask IoU is nearly blind to on large objects: Cheng et
+al., "Boundary IoU" (CVPR 2021) and the published mask_to_boundary routine, restated as in ytvis_eval.py.  A mask's band is
+Bd = M & ~E, E = M eroded d times by a 3 x 3 square with everything outside the image counting as 0, d = max(1,
+round(dilation_ratio * sqrt(H^2 + W^2))) of the mask's OWN image.  A pair's boundary IoU is |Bd(d) & Bd(g)| / |Bd(d) | Bd(g)|, and
+|Bd(d) & Bd(g)| / |Bd(d)| against a crowd (the crowd rule applied to the bands); the IoU that enters matching is min(mask IoU,
+boundary IoU); areas stay mask areas.  Per chunk that is two more launches: the bands of all planes of all images, each with its
+own size and d (csrc/mask_boundary.hip, erode_ragged_kernel), and the mask-IoU kernel a second time on the band buffer through the
+same tables.  An image whose band is wider than 64 pixels (a diagonal above about 3200 px at ratio 0.02) takes the chained
+per-image call instead.  Restated; parity with the boundary_iou package is unpinned.
+
+    python -m s2d_amd.coco_eval --gt ann.json --results res.json [--iou-type segm|bbox|boundary] [--dilation-ratio 0.02] [--use-cats]
 """
 import argparse
 import itertools
@@ -40,7 +50,9 @@ AREA_RNG = [[0, 1e10], [0, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e10]]
 AREA_LBL = ["all", "small", "medium", "large"]
 METRICS = ["AP", "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10", "AR100", "ARs", "ARm", "ARl"]
 CHUNK_WORDS = 1 << 26          # plane words of one chunk (256 MiB): about 60 COCO-val images with 100 detections each.  The per-image
-#                                planes are concatenated into the flat buffer the kernel reads, so the peak is about twice this
+#                                planes are concatenated into the flat buffer the kernel reads, so the peak is about twice this.
+#                                "boundary" keeps a third copy, the bands, and counts an image's words double against the limit: a
+#                                chunk then holds half the words and the peak is 3 x half = about 1.5 times this (384 MiB)
 CHUNK_IMAGES = 1024
 LIB_CALLS = Counter()          # library calls made for this module, by export name ("decode": the per-image decode / bbox calls)
 
@@ -78,13 +90,13 @@ def _image_table(Ds, Gs):
 
 
 # --------------------------------------------------------------------------------------------------------------- device
-def mask_iou_ragged(planes, crowd, device=None):
-    """planes: per image (dt_bits int32 CUDA [D, wpp] or None, gt_bits [G, wpp] or None, H, W) in the layout of
-    ytvis_eval.decode_frames; crowd: per image the G crowd flags.  One launch (s2d_coco_mask_iou_ragged) ->
-    SimpleNamespace(iou f64 CUDA [P], inter int64 CUDA [P], area_d / area_g int32 CUDA, img, dt0, gt0, pair0 host tables)"""
+def stage_planes(planes, crowd, device=None):
+    """the chunk's planes concatenated ONCE into the flat buffer the kernels read, and the tables uploaded once (arguments as
+    mask_iou_ragged's) -> SimpleNamespace(bits int32 CUDA [words] or None for a chunk without planes, words, N, img / dt0 / gt0 /
+    pair0 host tables, img_dev, tiles_dev, n_tiles, crowd_dev, dev): what mask_iou_staged reads, on `bits` or on any buffer of
+    the same layout (the boundary bands)"""
     import torch
     from . import ops
-    from ._lib import lib
     dev = _device(device)
     Ds = [0 if p[0] is None else int(p[0].shape[0]) for p in planes]
     Gs = [0 if p[1] is None else int(p[1].shape[0]) for p in planes]
@@ -110,16 +122,75 @@ def mask_iou_ragged(planes, crowd, device=None):
     crowd_h = np.concatenate([np.asarray(c, np.uint8).reshape(-1) for c in crowd]) if len(crowd) else np.zeros(0, np.uint8)
     if len(crowd) != len(planes) or crowd_h.size != gt0[-1] or any(len(c) != g for c, g in zip(crowd, Gs)):
         raise ValueError("crowd flags do not match the ground-truth planes")
-    out = SimpleNamespace(iou=torch.empty((int(pair0[-1]),), device=dev, dtype=torch.float64),
-                          inter=torch.empty((int(pair0[-1]),), device=dev, dtype=torch.int64),
-                          area_d=torch.empty((int(dt0[-1]),), device=dev, dtype=torch.int32),
-                          area_g=torch.empty((int(gt0[-1]),), device=dev, dtype=torch.int32), img=img, dt0=dt0, gt0=gt0, pair0=pair0)
+    st = SimpleNamespace(bits=None, words=word, N=len(planes), img=img, dt0=dt0, gt0=gt0, pair0=pair0, img_dev=None, tiles_dev=None,
+                         n_tiles=0, crowd_dev=None, dev=dev)
     if tiles:
         tiles_h = np.concatenate(tiles).astype(np.int32)
-        bits = torch.cat(parts) if len(parts) > 1 else parts[0]
-        assert bits.numel() == word
-        _lib_call("s2d_coco_mask_iou_ragged", bits, _up(img, dev), len(planes), _up(tiles_h, dev), len(tiles_h), _up(crowd_h, dev),
+        st.bits = torch.cat(parts) if len(parts) > 1 else parts[0]
+        assert st.bits.numel() == word
+        st.img_dev, st.tiles_dev, st.n_tiles, st.crowd_dev = _up(img, dev), _up(tiles_h, dev), len(tiles_h), _up(crowd_h, dev)
+    return st
+
+
+def mask_iou_staged(st, bits=None):
+    """One launch (s2d_coco_mask_iou_ragged) on the staged chunk `st`, reading st.bits or `bits`, an int32 CUDA buffer of the same
+    layout -> the SimpleNamespace mask_iou_ragged documents"""
+    import torch
+    from . import ops
+    dev = st.dev
+    out = SimpleNamespace(iou=torch.empty((int(st.pair0[-1]),), device=dev, dtype=torch.float64),
+                          inter=torch.empty((int(st.pair0[-1]),), device=dev, dtype=torch.int64),
+                          area_d=torch.empty((int(st.dt0[-1]),), device=dev, dtype=torch.int32),
+                          area_g=torch.empty((int(st.gt0[-1]),), device=dev, dtype=torch.int32), img=st.img, dt0=st.dt0, gt0=st.gt0,
+                          pair0=st.pair0)
+    if st.n_tiles:
+        bits = st.bits if bits is None else bits
+        ops._chk(bits, torch.int32)
+        if bits.dim() != 1 or bits.numel() != st.words or bits.device != st.bits.device:
+            raise ValueError(f"a buffer of {tuple(bits.shape)} words for a chunk of {st.words}")
+        _lib_call("s2d_coco_mask_iou_ragged", bits, st.img_dev, st.N, st.tiles_dev, st.n_tiles, st.crowd_dev,
                    out.inter, out.area_d, out.area_g, out.iou, ops._stream())
+    return out
+
+
+def mask_iou_ragged(planes, crowd, device=None):
+    """planes: per image (dt_bits int32 CUDA [D, wpp] or None, gt_bits [G, wpp] or None, H, W) in the layout of
+    ytvis_eval.decode_frames; crowd: per image the G crowd flags.  One launch (s2d_coco_mask_iou_ragged) ->
+    SimpleNamespace(iou f64 CUDA [P], inter int64 CUDA [P], area_d / area_g int32 CUDA, img, dt0, gt0, pair0 host tables)"""
+    return mask_iou_staged(stage_planes(planes, crowd, device))
+
+
+def boundary_bands_ragged(bits, spec, out=None):
+    """The boundary bands of a chunk's planes in one launch (s2d_mask_boundary_ragged_plan + s2d_mask_boundary_ragged_u32).
+    bits: int32 CUDA [words], the flat buffer of stage_planes; spec: host int64 [N, 5] = {word0, F, H, W, d} per image (F planes of
+    ceil(H*W/32) words from word0; F = 0: an image this call leaves out).  -> int32 CUDA [words] (`out` if given): every listed plane's
+    band M & ~erode(M, d) at the plane's own offset, padding bits 0; words of no listed plane are 0 or untouched (include/s2d_hip.h).
+    Every table entry is checked against the buffer before the launch; a clamped d above 64 is refused (boundary_planes chains)."""
+    import torch
+    from . import ops
+    ops._chk(bits, torch.int32)
+    if bits.dim() != 1:
+        raise ValueError(f"boundary_bands_ragged: a flat buffer, not {tuple(bits.shape)}")
+    spec = np.ascontiguousarray(spec, np.int64).reshape(-1, 5)
+    N, words = len(spec), bits.numel()
+    if N:
+        word0, F, H, W, d = spec.T
+        ok = (F >= 0).all() and (H >= 1).all() and (W >= 1).all() and (H < 1 << 31).all() and (W < 1 << 31).all() and (d >= 1).all()
+        ok = ok and (H * W < 1 << 31).all() and (np.minimum(d, (np.minimum(H, W) + 1) // 2) <= 64).all()
+        if ok:
+            end = word0 + F * ((H * W + 31) // 32)
+            ok = word0[0] >= 0 and (word0[1:] >= end[:-1]).all() and (end <= words).all() and (word0 <= words).all()
+        if not ok:
+            raise ValueError("boundary_bands_ragged: inconsistent tables")
+    if out is None:
+        out = torch.empty_like(bits)
+    ops._chk(out, torch.int32)
+    if out.shape != bits.shape or out.device != bits.device or out.data_ptr() == bits.data_ptr():
+        raise ValueError("boundary_bands_ragged: out must be a second buffer of the same size on the same device")
+    if N and words:
+        plan, nwg, lds = np.zeros((N, 12), np.int64), np.zeros(1, np.int64), np.zeros(1, np.int64)
+        _lib_call("s2d_mask_boundary_ragged_plan", spec, N, words, plan, nwg, lds)
+        _lib_call("s2d_mask_boundary_ragged_u32", bits, words, plan, _up(plan, bits.device), N, out, ops._stream())
     return out
 
 
@@ -399,15 +470,20 @@ def _box_area(boxes):
 
 
 def evaluate_coco(gt, results, *, iou_type="segm", use_cats=False, max_dets=(1, 10, 100), device=None, matcher="device",
-                  profile=False):
+                  profile=False, dilation_ratio=0.02):
     """Score a COCO results list / file ({image_id, category_id, score, segmentation and/or bbox}) against a COCO instances
     document / file.  Returns the COCOEval after evaluate + accumulate (call .summarize() for the table and .stats).
     matcher="host": the Python matching loop on the device-computed IoUs (reference path).  profile: synchronise between the
     phases so that `.seconds` (decode, iou, match, accumulate) are device-inclusive times; `.launches` counts the library calls made ("decode": RLE parse,
-    RLE decode, polygon fill and plane-bbox calls, per image; "iou" and "match": one per non-empty chunk) either way."""
+    RLE decode, polygon fill and plane-bbox calls, per image; "iou" and "match": one per non-empty chunk) either way.
+    iou_type="boundary": Boundary AP -- matching on min(mask IoU, boundary IoU), the bands `dilation_ratio` of each image's
+    diagonal wide; `.seconds["boundary"]` is the band phase, `.launches["boundary"]` the ragged band calls (one per non-empty chunk),
+    `.launches["boundary_chained"]` the images whose band is wider than 64 pixels and goes through boundary_planes, and
+    `.launches["iou"]` is 2 per non-empty chunk (masks, bands)."""
     import torch
-    if iou_type not in ("segm", "bbox"):
-        raise ValueError(f"iou_type {iou_type!r}: 'segm' or 'bbox'")
+    from .ytvis_eval import boundary_dilation, boundary_planes
+    if iou_type not in ("segm", "bbox", "boundary"):
+        raise ValueError(f"iou_type {iou_type!r}: 'segm', 'bbox' or 'boundary'")
     if isinstance(results, (str, os.PathLike)):
         with open(results) as fh:
             results = json.load(fh)
@@ -419,7 +495,8 @@ def evaluate_coco(gt, results, *, iou_type="segm", use_cats=False, max_dets=(1, 
             raise ValueError(f"results for image {r['image_id']}, which the ground truth does not have")
         by_img[r["image_id"]].append(n)
     ev = COCOEval(gt, iou_type, use_cats, max_dets)
-    segm = iou_type == "segm"
+    boundary = iou_type == "boundary"
+    segm = iou_type == "segm" or boundary
 
     def tick(name, t0):
         if profile:
@@ -436,9 +513,29 @@ def evaluate_coco(gt, results, *, iou_type="segm", use_cats=False, max_dets=(1, 
         if any(s is None for s, _ in entries) if segm else any(s is None and b is None for s, b in entries):
             raise ValueError(f"image {iid}: a result or annotation without a segmentation" + ("" if segm else " or bbox"))
         need = list(range(len(entries))) if segm else [k for k, (_, b) in enumerate(entries) if b is None]     # planes to decode
-        words = len(need) * ((im["height"] * im["width"] + 31) // 32)
+        words = len(need) * ((im["height"] * im["width"] + 31) // 32) * (2 if boundary else 1)        # the bands are a copy more
         return SimpleNamespace(iid=iid, H=im["height"], W=im["width"], idx=idx, gts=gts, dsegs=dsegs, gsegs=gsegs, dbox=dbox, gbox=gbox,
                                need=need, words=words)
+
+    def bands(chunk, st):
+        """the chunk's boundary bands in the layout of st.bits: one ragged call, and boundary_planes for an image whose band is
+        wider than one pass takes (written after the ragged call, which may zero the whole buffer)"""
+        spec, chained = np.zeros((len(chunk), 5), np.int64), []
+        for n, c in enumerate(chunk):
+            d = boundary_dilation(c.H, c.W, dilation_ratio)
+            one_pass = min(d, (min(c.H, c.W) + 1) // 2) <= 64
+            F = int(st.img[n, 4] + st.img[n, 5])
+            spec[n] = st.img[n, 0], F if one_pass else 0, c.H, c.W, d if one_pass else 1
+            if F and not one_pass:
+                chained.append((n, c, d))
+        before = LIB_CALLS["s2d_mask_boundary_ragged_u32"]
+        band = boundary_bands_ragged(st.bits, spec)
+        ev.launches["boundary"] += LIB_CALLS["s2d_mask_boundary_ragged_u32"] - before
+        for n, c, d in chained:
+            w0 = int(st.img[n, 0])
+            band[w0:w0 + c.bits.numel()] = boundary_planes(c.bits, c.H, c.W, d).reshape(-1)
+            ev.launches["boundary_chained"] += 1
+        return band
 
     def run(chunk):
         t0 = time.perf_counter()
@@ -452,8 +549,15 @@ def evaluate_coco(gt, results, *, iou_type="segm", use_cats=False, max_dets=(1, 
         calls = LIB_CALLS["s2d_coco_mask_iou_ragged"] + LIB_CALLS["s2d_coco_box_iou_ragged"]
         if segm:
             D = [len(c.idx) for c in chunk]
-            r = mask_iou_ragged([(c.bits[:d] if c.bits is not None else None, c.bits[d:] if c.bits is not None else None, c.H, c.W)
-                                 for c, d in zip(chunk, D)], crowd, dev)
+            st = stage_planes([(c.bits[:d] if c.bits is not None else None, c.bits[d:] if c.bits is not None else None, c.H, c.W)
+                               for c, d in zip(chunk, D)], crowd, dev)
+            r = mask_iou_staged(st)
+            if boundary and st.bits is not None:
+                tick("iou", t0)
+                t0 = time.perf_counter()
+                r.iou = torch.minimum(r.iou, mask_iou_staged(st, bands(chunk, st)).iou)
+                tick("boundary", t0)              # the band IoU launch and the min are booked here: "iou" stays what "segm" spends
+                t0 = time.perf_counter()
             d_area, g_pix = r.area_d.cpu().numpy().astype(np.float64), r.area_g.cpu().numpy()
         else:
             boxes = []
@@ -500,15 +604,18 @@ class COCOImageEvaluator:
     tensor [K,1,H,W] or as CPU bool tensors -- and keeps its results entries; `evaluate()` gathers the ranks' entries, orders
     them by the ground truth's image order, writes output_dir/coco_instances_results.json and returns {"segm": {...},
     "bbox": {...}} (12 metrics x 100 each; the boxes are the tight boxes of the masks).  On a document without `annotations`
-    it only writes the results.  Categories are pooled (use_cats=False), as in evaluate_ytvis."""
+    it only writes the results.  Categories are pooled (use_cats=False), as in evaluate_ytvis.  iou_types may also hold
+    "boundary" (opt-in): Boundary AP with bands `dilation_ratio` of the image diagonal wide, a dict of the same 12 names."""
 
-    def __init__(self, json_file=None, output_dir=None, distributed=True, iou_types=("segm", "bbox"), dataset_id_to_contiguous_id=None):
+    def __init__(self, json_file=None, output_dir=None, distributed=True, iou_types=("segm", "bbox"), dataset_id_to_contiguous_id=None,
+                 dilation_ratio=0.02):
         if json_file is None:
             raise ValueError("COCOImageEvaluator needs json_file= (a path or a loaded document)")
         for t in iou_types:
-            if t not in ("segm", "bbox"):
-                raise ValueError(f"iou type {t!r}: 'segm' or 'bbox'")
+            if t not in ("segm", "bbox", "boundary"):
+                raise ValueError(f"iou type {t!r}: 'segm', 'bbox' or 'boundary'")
         self._distributed, self._output_dir, self._iou_types = distributed, output_dir, tuple(iou_types)
+        self._dilation_ratio = dilation_ratio
         self._gt = COCOGroundTruth(json_file)
         self._do_evaluation = self._gt.has_annotations
         self._reverse = None
@@ -575,7 +682,7 @@ class COCOImageEvaluator:
             _log.info("Annotations are not available for evaluation.")
             return results
         for t in self._iou_types:
-            ev = evaluate_coco(self._gt, records, iou_type=t)
+            ev = evaluate_coco(self._gt, records, iou_type=t, dilation_ratio=self._dilation_ratio)
             ev.summarize()
             self.coco_eval[t] = ev
             results[t] = derive_results(ev.stats)
@@ -586,10 +693,11 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description="COCO image mask / box AP and AR of a results file")
     ap.add_argument("--gt", required=True, help="COCO instances JSON")
     ap.add_argument("--results", required=True, help="results JSON (list of {image_id, category_id, score, segmentation and/or bbox})")
-    ap.add_argument("--iou-type", choices=("segm", "bbox"), default="segm")
+    ap.add_argument("--iou-type", choices=("segm", "bbox", "boundary"), default="segm")
+    ap.add_argument("--dilation-ratio", type=float, default=0.02, help="boundary band width as a fraction of the image diagonal")
     ap.add_argument("--use-cats", action="store_true", help="per-category matching (the stock COCO protocol); default pools categories")
     a = ap.parse_args(argv)
-    evaluate_coco(a.gt, a.results, iou_type=a.iou_type, use_cats=a.use_cats).summarize()
+    evaluate_coco(a.gt, a.results, iou_type=a.iou_type, use_cats=a.use_cats, dilation_ratio=a.dilation_ratio).summarize()
 
 
 if __name__ == "__main__":

@@ -23,7 +23,13 @@
 // also with the zero border (an eroded plane is zero outside the image like its input).  The intermediates alternate between
 // the caller's workspace and `out`, the last one in the workspace.  A window that does not fit the image (2d+1 > min(H, W))
 // leaves E empty whatever d is, so d is first clamped to (min(H, W) + 1) / 2: no frame of the evaluator needs a second pass.
+//
+//   erode_ragged_kernel  the same tile body for a chunk of images of different sizes in ONE launch (the COCO image evaluator,
+//     s2d_amd/coco_eval.py): every image has its own H, W, d and tile shape, listed in a plan table that the host derives and
+//     re-checks before the launch; one pass only (clamped d <= 64), the last one: out = M & ~E.
 #include "common.h"
+
+#include <vector>
 
 namespace {
 
@@ -92,22 +98,17 @@ __device__ __forceinline__ unsigned int row_word(const uint32_t *__restrict__ pl
     return n >= 32 ? v : (v & ((1u << n) - 1u));            // 1 <= n: the word starts inside the row
 }
 
-// src: planes to erode by r; orig: planes M for the last pass (dst = M & ~E) or null (dst = E).  Workgroup b: plane
-// b / (ntx * nty), row tile (b / ntx) % nty, word tile b % ntx.  Dynamic LDS: 2 * TW * (TR + 2r) words.
-__global__ __launch_bounds__(BD_T) void erode_tile_kernel(const uint32_t *__restrict__ src, const uint32_t *__restrict__ orig,
-                                                          uint32_t *__restrict__ dst, int H, int W, int r, long wpf, int S,
-                                                          int TW, int TR, int ntx, int nty, int aligned)
+// One tile (row tile ty, word tile tx) of ONE plane: pl the plane to erode by r, ml the plane M for the last pass (op = M & ~E)
+// or null (op = E), op the output plane; lds: 2 * TW * (TR + 2r) words.  The body both kernels below share.
+__device__ __forceinline__ void erode_tile(const uint32_t *__restrict__ pl, const uint32_t *__restrict__ ml, uint32_t *__restrict__ op,
+                                           int H, int W, int r, long wpf, int S, int TW, int TR, int ty, int tx, int aligned,
+                                           unsigned int *lds)
 {
-    extern __shared__ unsigned int lds[];
-    const unsigned int nb = (unsigned int)ntx * nty;
-    const unsigned int f = blockIdx.x / nb, t = blockIdx.x - f * nb;
-    const int ty = t / ntx, tx = t - ty * ntx;
     const int y0 = ty * TR, k0 = tx * TW;
     const int LR = TR + 2 * r, N = TW * LR;
     const int n = 2 * r + 1;
     int p = 2;
     while (2 * p <= n) p *= 2;                              // largest power of two <= n (n >= 3)
-    const uint32_t *pl = src + (long)f * wpf;
     unsigned int *cur = lds, *nxt = lds + N;
 
     for (int i = threadIdx.x; i < N; i += BD_T) {
@@ -130,8 +131,6 @@ __global__ __launch_bounds__(BD_T) void erode_tile_kernel(const uint32_t *__rest
         unsigned int *s = cur; cur = nxt; nxt = s;
     }
     const int sh = (n - p) * TW;
-    uint32_t *op = dst + (long)f * wpf;
-    const uint32_t *ml = orig ? orig + (long)f * wpf : nullptr;
     for (int i = threadIdx.x; i < TR * TW; i += BD_T) {      // output row y0 + ry: window rows ry .. ry + 2r of the tile
         const int ry = i / TW, k = k0 + (i - ry * TW), y = y0 + ry;
         if (y >= H || k >= S) continue;
@@ -147,6 +146,54 @@ __global__ __launch_bounds__(BD_T) void erode_tile_kernel(const uint32_t *__rest
             if (hi) atomicOr(&op[(P >> 5) + 1], hi);
         }
     }
+}
+
+// src: planes to erode by r; orig: planes M for the last pass (dst = M & ~E) or null (dst = E).  Workgroup b: plane
+// b / (ntx * nty), row tile (b / ntx) % nty, word tile b % ntx.  Dynamic LDS: 2 * TW * (TR + 2r) words.
+__global__ __launch_bounds__(BD_T) void erode_tile_kernel(const uint32_t *__restrict__ src, const uint32_t *__restrict__ orig,
+                                                          uint32_t *__restrict__ dst, int H, int W, int r, long wpf, int S,
+                                                          int TW, int TR, int ntx, int nty, int aligned)
+{
+    extern __shared__ unsigned int lds[];
+    const unsigned int nb = (unsigned int)ntx * nty;
+    const unsigned int f = blockIdx.x / nb, t = blockIdx.x - f * nb;
+    const int ty = t / ntx, tx = t - ty * ntx;
+    erode_tile(src + (long)f * wpf, orig ? orig + (long)f * wpf : nullptr, dst + (long)f * wpf, H, W, r, wpf, S, TW, TR, ty, tx,
+               aligned, lds);
+}
+
+constexpr int RP_COLS = 12;         // plan row: word0 F H W d wpp S TW TR ntx nty wg0 (include/s2d_hip.h)
+
+// The band of every plane of a chunk of N images of different sizes, one pass (every d <= 64).  Workgroup b belongs to the
+// last image n with wg0[n] <= b (binary search over the plan rows; an image without planes shares its wg0 with its successor
+// and is never found), and inside it to plane (b - wg0) / (ntx * nty), row tile ((b - wg0) / ntx) % nty, word tile
+// (b - wg0) % ntx.  Everything a workgroup reads from the plan is uniform over it; the tile body is erode_tile with the image's
+// own H, W, d, TW, TR.
+// Occupancy: dynamic LDS is one figure per launch, the largest 2 * TW * (TR + 2d) words of any image, so one large image in
+// the chunk sets the residency of every workgroup: at the 64 KiB of a tile that fills the cap, two workgroups (8 waves) per CU
+// of 160 KiB, also for the workgroups of a 32 x 32 image that use a few hundred bytes and, launched alone, would be resident
+// up to the wave limit.  A small image's workgroup is short (one or two trips per loop), so what it loses is overlap of its
+// load latency, not capacity; a chunk of small images only gets a small figure.
+__global__ __launch_bounds__(BD_T) void erode_ragged_kernel(const uint32_t *__restrict__ bits, uint32_t *__restrict__ out,
+                                                            const long *__restrict__ plan, int N)
+{
+    extern __shared__ unsigned int lds[];
+    const long b = blockIdx.x;
+    int lo = 0, hi = N;                                     // answer in [lo, hi)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (plan[(long)RP_COLS * mid + 11] <= b) lo = mid; else hi = mid;
+    }
+    const long *q = plan + (long)RP_COLS * lo;
+    const int H = (int)q[2], W = (int)q[3], r = (int)q[4], S = (int)q[6], TW = (int)q[7], TR = (int)q[8];
+    const int ntx = (int)q[9], nty = (int)q[10];
+    const long wpp = q[5];
+    const unsigned int local = (unsigned int)(b - q[11]), nb = (unsigned int)ntx * nty;
+    const unsigned int f = local / nb, t = local - f * nb;
+    if ((long)f >= q[1]) return;                            // not reached with a plan the host call accepted
+    const int ty = t / ntx, tx = t - ty * ntx;
+    const long at = q[0] + (long)f * wpp;
+    erode_tile(bits + at, bits + at, out + at, H, W, r, wpp, S, TW, TR, ty, tx, (W & 31) == 0, lds);
 }
 
 struct BdPlan { int d, TW, TR, ntx, nty, S; long wpf, nb; };
@@ -173,9 +220,65 @@ bool bd_plan(int F, int H, int W, int d, BdPlan *pp)
     return true;
 }
 
+// spec [N][5] = {word0, F, H, W, d} -> plan rows, total workgroups, launch LDS bytes; false (nothing written) for a table the
+// ragged call refuses.  rows may be null (validation only).
+bool ragged_plan(const long *spec, int N, long total_words, long *rows, long *n_wg, long *lds_bytes)
+{
+    if (N < 0 || total_words < 0 || (N > 0 && !spec)) return false;
+    for (int pass = 0; pass < 2; ++pass) {                  // pass 0 checks everything, pass 1 writes
+        long end = 0, wg = 0, lds = 0;
+        for (int n = 0; n < N; ++n) {
+            const long *s = spec + 5L * n;
+            const long word0 = s[0], F = s[1], H = s[2], W = s[3], d = s[4];
+            if (F < 0 || F >= (1L << 31) || H < 1 || W < 1 || H >= (1L << 31) || W >= (1L << 31) || d < 1) return false;
+            BdPlan q;
+            if (!bd_plan((int)F, (int)H, (int)W, (int)(d < (1L << 30) ? d : (1L << 30)), &q) || q.d > BD_RMAX) return false;
+            if (word0 < end || word0 > total_words || F > (total_words - word0) / q.wpf) return false;   // ascending, disjoint, inside
+            end = word0 + F * q.wpf;
+            const long bytes = 2L * q.TW * (q.TR + 2 * q.d) * (long)sizeof(unsigned int);
+            if (bytes > 65536) return false;
+            if (F && bytes > lds) lds = bytes;
+            if (pass && rows) {
+                const long row[RP_COLS] = {word0, F, H, W, q.d, q.wpf, q.S, q.TW, q.TR, q.ntx, q.nty, wg};
+                for (int c = 0; c < RP_COLS; ++c) rows[(long)RP_COLS * n + c] = row[c];
+            }
+            wg += F * q.nb;
+            if (wg >= (1L << 31)) return false;
+        }
+        if (pass) { *n_wg = wg; *lds_bytes = lds; }
+    }
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
+
+int s2d_mask_boundary_ragged_plan(const long *spec, int N, long total_words, long *plan, long *n_workgroups, long *lds_bytes)
+{
+    if (!n_workgroups || !lds_bytes || (N > 0 && !plan)) return S2D_ERR_ARG;
+    return ragged_plan(spec, N, total_words, plan, n_workgroups, lds_bytes) ? S2D_OK : S2D_ERR_ARG;
+}
+
+int s2d_mask_boundary_ragged_u32(const uint32_t *bits, long total_words, const long *plan_host, const long *plan_dev, int N,
+                                 uint32_t *out, hipStream_t stream)
+{
+    if (N < 0 || total_words < 0 || !bits || !out || bits == out || !plan_host || !plan_dev) return S2D_ERR_ARG;
+    std::vector<long> spec(5 * (size_t)N), rows((size_t)RP_COLS * N);
+    for (int n = 0; n < N; ++n)
+        for (int c = 0; c < 5; ++c) spec[5 * (size_t)n + c] = plan_host[(size_t)RP_COLS * n + c];
+    long n_wg = 0, lds = 0;
+    if (!ragged_plan(spec.data(), N, total_words, rows.data(), &n_wg, &lds)) return S2D_ERR_ARG;
+    for (size_t i = 0; i < rows.size(); ++i)
+        if (rows[i] != plan_host[i]) return S2D_ERR_ARG;     // a table that is not what the plan call wrote: nothing is launched
+    if (n_wg == 0) return S2D_OK;
+    bool unaligned = false;
+    for (int n = 0; n < N; ++n) unaligned |= rows[(size_t)RP_COLS * n + 1] > 0 && (rows[(size_t)RP_COLS * n + 3] & 31) != 0;
+    if (unaligned && s2d_zero_async(out, sizeof(uint32_t) * (size_t)total_words, stream) != S2D_OK) return S2D_ERR_LAUNCH;
+    hipLaunchKernelGGL(erode_ragged_kernel, dim3((unsigned)n_wg), dim3(BD_T), (size_t)lds, stream, bits, out, plan_dev, N);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
 
 long s2d_mask_boundary_workspace_words(int F, int H, int W, int d)
 {

@@ -17,7 +17,9 @@ rank and rank 0 writes the files.
 data/image_clip.detect_train_format): a COCO instances document is scored image by image -- every image a one-frame video through
 the same `model([inputs])` (data/coco_image_loader.COCOImageTestLoader, coco_eval.COCOImageEvaluator) -- and the run writes
 OUT/coco_instances_results.json and OUT/metrics.json as {"segm": ..., "bbox": ...} (mask AP and box AP of the masks' tight boxes,
-12 metrics each); the timing line counts `images`.  --boundary-ap is a YTVIS option: with the image format it is refused."""
+12 metrics each); the timing line counts `images`.  --iou-types segm,bbox[,boundary] (image format only; default segm,bbox) chooses
+the dicts of metrics.json: `boundary` adds Boundary AP (coco_eval.py), bands --dilation-ratio of the image diagonal wide.
+--boundary-ap is a YTVIS option: with the image format it is refused (--iou-types is the image format's switch)."""
 import argparse
 import json
 import os
@@ -39,6 +41,7 @@ def parse_args(argv=None):
     ap.add_argument("--dist-backend", default="gloo", help="process group backend under torch.distributed.run")
     ap.add_argument("--boundary-ap", action="store_true", help="also score Boundary AP (matching on min(mask IoU, boundary IoU))")
     ap.add_argument("--dilation-ratio", type=float, default=0.02, help="boundary band width as a fraction of the image diagonal")
+    ap.add_argument("--iou-types", default=None, help="image format only: comma-separated list of segm, bbox, boundary (default segm,bbox)")
     ap.add_argument("--test-format", choices=("auto", "ytvis", "coco_image"), default="auto",
                     help="the --gt document: YTVIS videos or COCO images (auto: `images` without `videos` is coco_image)")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="config overrides KEY VALUE ...")
@@ -61,24 +64,44 @@ def build_model(cfg, weights, device):
     return model
 
 
-def resolve_test_format(fmt, doc, boundary=False):
-    """--test-format -> "ytvis" or "coco_image" for the loaded --gt document; --boundary-ap with the image format is refused"""
+IOU_TYPES = ("segm", "bbox", "boundary")
+
+
+def parse_iou_types(text):
+    """--iou-types -> tuple of names in the order given (None: the default ("segm", "bbox")); unknown, repeated or no names are
+    refused"""
+    if text is None:
+        return ("segm", "bbox")
+    names = tuple(t.strip() for t in (text.split(",") if isinstance(text, str) else text))
+    if not names or any(t not in IOU_TYPES for t in names) or len(set(names)) != len(names):
+        raise ValueError(f"--iou-types {text!r}: a comma-separated list of distinct names from {', '.join(IOU_TYPES)}")
+    return names
+
+
+def resolve_test_format(fmt, doc, boundary=False, iou_types=None):
+    """--test-format -> "ytvis" or "coco_image" for the loaded --gt document; --boundary-ap with the image format is refused, and
+    so is --iou-types (anything but None) with the YTVIS format"""
     from .data.image_clip import detect_train_format
     if fmt not in ("auto", "ytvis", "coco_image"):
         raise ValueError(f"test format {fmt!r}: auto, ytvis or coco_image")
     fmt = detect_train_format(doc) if fmt == "auto" else fmt
     if fmt == "coco_image" and boundary:
-        raise ValueError("--boundary-ap scores YTVIS videos: it is not available with --test-format coco_image")
+        raise ValueError("--boundary-ap scores YTVIS videos: it is not available with --test-format coco_image "
+                         "(Boundary AP of images: --iou-types segm,bbox,boundary)")
+    if fmt != "coco_image" and iou_types is not None:
+        raise ValueError("--iou-types chooses the tables of a COCO image split: it is not available with --test-format ytvis "
+                         "(Boundary AP of videos: --boundary-ap)")
     return fmt
 
 
 def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, prefetch=2, boundary=False, dilation_ratio=0.02,
-                   test_format="ytvis"):
+                   test_format="ytvis", iou_types=None):
     """score `model` on a YTVIS split: every video through `model([inputs])` (eval mode, predictions as COCO RLE) with the test
     loader and YTVISEvaluator; writes output_dir/results.json and, on rank 0 of a split with annotations, output_dir/metrics.json
     (boundary: Boundary AP as well, and metrics.json holds {"segm", "boundary"}).
     test_format "coco_image" ("auto": decided by the document): a COCO image split instead -- COCOImageTestLoader and
-    COCOImageEvaluator, files output_dir/coco_instances_results.json and metrics.json = {"segm", "bbox"}, `images` in the timing line.
+    COCOImageEvaluator, files output_dir/coco_instances_results.json and metrics.json = {"segm", "bbox"}, `images` in the timing line;
+    iou_types (image format only; None: ("segm", "bbox")) chooses those dicts, "boundary" among them.
     The model's training mode and inference_rle switch are restored afterwards.  -> (results, timing line dict)"""
     from .data.test_loader import YTVISTestLoader
     from .ytvis_eval import YTVISEvaluator
@@ -89,11 +112,13 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
             gt = json.load(fh)
     # labels -> dataset category ids as the registered dataset's metadata maps them (load_ytvis_json: sorted ids, contiguous)
     id_map = {c: i for i, c in enumerate(sorted(c["id"] for c in gt.get("categories", [])))} or None
-    images = resolve_test_format(test_format, gt, boundary) == "coco_image"
+    images = resolve_test_format(test_format, gt, boundary, iou_types) == "coco_image"
+    iou_types = parse_iou_types(iou_types)
     if images:
         from .coco_eval import COCOImageEvaluator
         from .data.coco_image_loader import COCOImageTestLoader
-        evaluator = COCOImageEvaluator(json_file=gt, distributed=True, output_dir=output_dir, dataset_id_to_contiguous_id=id_map)
+        evaluator = COCOImageEvaluator(json_file=gt, distributed=True, output_dir=output_dir, dataset_id_to_contiguous_id=id_map,
+                                       iou_types=iou_types, dilation_ratio=dilation_ratio)
         loader = COCOImageTestLoader.from_config(cfg, gt, image_root, device=device, threads=threads, prefetch=prefetch)
     else:
         evaluator = YTVISEvaluator(json_file=gt, distributed=True, output_dir=output_dir, dataset_id_to_contiguous_id=id_map,
@@ -124,10 +149,12 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
     results = evaluator.evaluate()
     if rank == 0:
         os.makedirs(output_dir, exist_ok=True)
-        if "segm" in results:
+        if images and results:
             with open(os.path.join(output_dir, "metrics.json"), "w") as fh:
-                json.dump({k: results[k] for k in (("segm", "bbox") if images else ("segm", "boundary"))} if boundary or images
-                          else results["segm"], fh)
+                json.dump({k: results[k] for k in iou_types}, fh)
+        elif "segm" in results:
+            with open(os.path.join(output_dir, "metrics.json"), "w") as fh:
+                json.dump({k: results[k] for k in ("segm", "boundary")} if boundary else results["segm"], fh)
     line = {"rank": rank, "images" if images else "videos": nvid, "frames": nfr, "windows": nwin, "wall_s": round(wall, 4),
             "images_per_s" if images else "videos_per_s": round(nvid / wall, 4) if wall > 0 else None,
             "frames_per_s": round(nfr / wall, 3) if wall > 0 else None,
@@ -149,10 +176,11 @@ def main(argv=None):
     cfg = load_config(a.config_file, a.opts)
     with open(a.gt) as fh:
         gt_doc = json.load(fh)
-    fmt = resolve_test_format(a.test_format, gt_doc, a.boundary_ap)
+    iou_types = parse_iou_types(a.iou_types) if a.iou_types is not None else None
+    fmt = resolve_test_format(a.test_format, gt_doc, a.boundary_ap, iou_types)
     model = build_model(cfg, a.weights or cfg.MODEL.WEIGHTS, device)
     results, line = evaluate_model(cfg, model, gt_doc, a.image_root, a.output_dir, device, a.threads, a.prefetch,
-                                   boundary=a.boundary_ap, dilation_ratio=a.dilation_ratio, test_format=fmt)
+                                   boundary=a.boundary_ap, dilation_ratio=a.dilation_ratio, test_format=fmt, iou_types=iou_types)
     print(json.dumps(line), flush=True)
     if dist.is_initialized():
         dist.barrier()
