@@ -430,6 +430,26 @@ int s2d_infer_masks_u8(const float *mask_logits, int ldq, int T, int hm, int wm,
                        int ow, const int *query, int K, float *workspace, uint8_t *masks, uint32_t *bits,
                        hipStream_t stream);
 
+/* Non-overlapping proposal index maps straight from the low-resolution logits (DAVIS unsupervised: one u8 label per pixel):
+ * v_k = the two-stage bilinear value s2d_infer_masks_u8 thresholds, for proposal k's column query[k], formed by the same device
+ * functions in the same float32 expression tree, so "proposal k holds the pixel" (v_k > 0; NaN and -0.0 hold nothing) is bit for
+ * bit masks[k] of that call.  index u8 [T][oh][ow], every byte written: 0 = no proposal holds the pixel, k + 1 = proposal k.
+ *   rule 0 ("rank")  1 + min{k : v_k > 0}: the best-ranked holder (query / score are in proposal order, best first, as
+ *                    s2d_infer_select_f32 returns them); score may be NULL
+ *   rule 1 ("prob")  among the holders, the k with the largest float32 score[k] / (1.f + expf(-v_k)); equal products: lower k
+ * mask_logits pixel-major [T*hm*wm][ldq]; query int32 [K] (repeats allowed; an entry outside [0, ldq) is clamped into it),
+ * score f32 [K], both on the device.  1 <= K <= 254 (255 is DAVIS' void label), ldq <= 128 and a multiple of 4, any oh / ow and
+ * any alignment of index; offsets into index are 64-bit.  Nothing of size [K][T][oh][ow] exists at any point and no workspace
+ * is needed: a workgroup stages the K selected columns of the logits under its 16 x 64 output tile in LDS, or, where K times
+ * that window exceeds 40 KB, reads the logits directly.  Bad arguments return S2D_ERR_ARG and launch nothing. */
+int s2d_infer_index_u8(const float *mask_logits, int ldq, int T, int hm, int wm, int Hp, int Wp, int ih, int iw,
+                       int oh, int ow, const int *query, const float *score, int K, int rule,
+                       uint8_t *index, hipStream_t stream);
+
+/* bytes of LDS a workgroup of that call stages its window in (K * the largest window of any tile * 4); 0: the call takes the
+ * direct path; -1: the sizes are refused */
+long s2d_infer_index_lds_bytes(int ldq, int T, int hm, int wm, int Hp, int Wp, int ih, int iw, int oh, int ow, int K);
+
 /* byte mask planes u8 [K][n] (0 / non-0) -> bit words [K][ceil(n/32)] in the layout above: feeds s2d_mask_pair_counts_u64 for
  * masks that exist as bytes -- the distillation pseudo targets under MODEL.MASK_FORMER.DISTILLATION_NMS
  * (kd_video_maskformer_model.py:484-520). */

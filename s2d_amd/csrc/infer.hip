@@ -87,7 +87,7 @@ struct ResizeParams {
 };
 
 // source index / weights of F.interpolate(mode="bilinear", align_corners=False)
-__device__ __forceinline__ void src_tap(float scale, int dst, int in_size, int &i0, int &i1, float &l0, float &l1)
+__host__ __device__ __forceinline__ void src_tap(float scale, int dst, int in_size, int &i0, int &i1, float &l0, float &l1)
 {
     float s = scale * (dst + 0.5f) - 0.5f;
     if (s < 0.f) s = 0.f;
@@ -102,6 +102,66 @@ __device__ __forceinline__ float stage1(const float *__restrict__ r0, const floa
                                         int x1, float hx, float lx)
 {
     return hy * (hx * r0[x0] + lx * r0[x1]) + ly * (hx * r1[x0] + lx * r1[x1]);
+}
+
+// The vertical half of one output row's taps: stage-1 rows under stage-2 row Y0 (qa0, qa1 with weights hya, lya) and, two-stage
+// only, under Y1 (qb0, qb1; hyb, lyb), with the stage-2 weights HY, LY (1, 0 when SAME: the second resize is the identity).
+struct RowTaps {
+    int qa0, qa1, qb0, qb1;
+    float hya, lya, hyb, lyb, HY, LY;
+};
+
+template <bool SAME>
+__device__ __forceinline__ RowTaps row_taps(float s1y, float s2y, int y, int hm, int ih)
+{
+    RowTaps r;
+    r.qb0 = r.qb1 = 0; r.hyb = r.lyb = 0.f; r.HY = 1.f; r.LY = 0.f;
+    if (SAME) {
+        src_tap(s1y, y, hm, r.qa0, r.qa1, r.hya, r.lya);
+    } else {
+        int Y0, Y1;
+        src_tap(s2y, y, ih, Y0, Y1, r.HY, r.LY);
+        src_tap(s1y, Y0, hm, r.qa0, r.qa1, r.hya, r.lya);
+        src_tap(s1y, Y1, hm, r.qb0, r.qb1, r.hyb, r.lyb);
+    }
+    return r;
+}
+
+// The horizontal half, per output column; the column indices come back multiplied by xs, the element stride of a low-resolution
+// row (1 in a gathered plane, ldq in the pixel-major logits) and shifted by -x_org (the first column a staged window holds).
+struct ColTaps {
+    int xa0, xa1, xb0, xb1;
+    float ha, la, hb, lb, HX, LX;
+};
+
+template <bool SAME>
+__device__ __forceinline__ ColTaps col_taps(float s1x, float s2x, int x, int wm, int iw, int x_org = 0, int xs = 1)
+{
+    ColTaps c;
+    c.xb0 = c.xb1 = 0; c.hb = c.lb = 0.f; c.HX = 1.f; c.LX = 0.f;
+    if (SAME) {
+        src_tap(s1x, x, wm, c.xa0, c.xa1, c.ha, c.la);
+    } else {
+        int X0, X1;
+        src_tap(s2x, x, iw, X0, X1, c.HX, c.LX);
+        src_tap(s1x, X0, wm, c.xa0, c.xa1, c.ha, c.la);
+        src_tap(s1x, X1, wm, c.xb0, c.xb1, c.hb, c.lb);
+        c.xb0 = (c.xb0 - x_org) * xs; c.xb1 = (c.xb1 - x_org) * xs;
+    }
+    c.xa0 = (c.xa0 - x_org) * xs; c.xa1 = (c.xa1 - x_org) * xs;
+    return c;
+}
+
+// The value of the two-stage resize at one output pixel, from the four low-resolution rows a0, a1 (under Y0), b0, b1 (under Y1):
+// THE float32 expression tree of masks and index maps alike (SAME: stage 1 alone).  Both kernels call this and nothing else, so
+// the sign of v, which is all either of them keeps of it, is the same bit in both.
+template <bool SAME>
+__device__ __forceinline__ float resize_value(const float *__restrict__ a0, const float *__restrict__ a1, const float *__restrict__ b0,
+                                              const float *__restrict__ b1, const RowTaps &r, const ColTaps &c)
+{
+    if (SAME) return stage1(a0, a1, r.hya, r.lya, c.xa0, c.xa1, c.ha, c.la);
+    return r.HY * (c.HX * stage1(a0, a1, r.hya, r.lya, c.xa0, c.xa1, c.ha, c.la) + c.LX * stage1(a0, a1, r.hya, r.lya, c.xb0, c.xb1, c.hb, c.lb)) +
+           r.LY * (c.HX * stage1(b0, b1, r.hyb, r.lyb, c.xa0, c.xa1, c.ha, c.la) + c.LX * stage1(b0, b1, r.hyb, r.lyb, c.xb0, c.xb1, c.hb, c.lb));
 }
 
 // A thread owns 4 consecutive elements of one mask (flat index over [T][oh][ow]); 8 lanes make one 32-bit word.  The
@@ -126,42 +186,20 @@ __global__ __launch_bounds__(256) void infer_resize_kernel(ResizeParams p)
         }
         // stage-1 rows (a: under stage-2 row Y0, b: under Y1; SAME uses a only) and the stage-2 vertical weights
         const float *a0 = nullptr, *a1 = nullptr, *b0 = nullptr, *b1 = nullptr;
-        float hya = 0.f, lya = 0.f, hyb = 0.f, lyb = 0.f, HY = 1.f, LY = 0.f;
+        RowTaps r;
 #define S2D_SET_ROW()                                                                           \
         do {                                                                                    \
             const float *pl = p.planes + ((long)k * p.T + t) * p.hm * p.wm;                     \
-            int q0, q1;                                                                         \
-            if (SAME) {                                                                         \
-                src_tap(p.s1y, y, p.hm, q0, q1, hya, lya);                                      \
-                a0 = pl + q0 * p.wm; a1 = pl + q1 * p.wm;                                       \
-            } else {                                                                            \
-                int Y0, Y1;                                                                     \
-                src_tap(p.s2y, y, p.ih, Y0, Y1, HY, LY);                                        \
-                src_tap(p.s1y, Y0, p.hm, q0, q1, hya, lya);                                     \
-                a0 = pl + q0 * p.wm; a1 = pl + q1 * p.wm;                                       \
-                src_tap(p.s1y, Y1, p.hm, q0, q1, hyb, lyb);                                     \
-                b0 = pl + q0 * p.wm; b1 = pl + q1 * p.wm;                                       \
-            }                                                                                   \
+            r = row_taps<SAME>(p.s1y, p.s2y, y, p.hm, p.ih);                                    \
+            a0 = pl + r.qa0 * p.wm; a1 = pl + r.qa1 * p.wm;                                     \
+            if (!SAME) { b0 = pl + r.qb0 * p.wm; b1 = pl + r.qb1 * p.wm; }                      \
         } while (0)
         S2D_SET_ROW();
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (i0 + j < p.N) {
-                float v;
-                int xa0, xa1;
-                float ha, la;
-                if (SAME) {
-                    src_tap(p.s1x, x, p.wm, xa0, xa1, ha, la);
-                    v = stage1(a0, a1, hya, lya, xa0, xa1, ha, la);
-                } else {
-                    int X0, X1, xb0, xb1;
-                    float HX, LX, hb, lb;
-                    src_tap(p.s2x, x, p.iw, X0, X1, HX, LX);
-                    src_tap(p.s1x, X0, p.wm, xa0, xa1, ha, la);
-                    src_tap(p.s1x, X1, p.wm, xb0, xb1, hb, lb);
-                    v = HY * (HX * stage1(a0, a1, hya, lya, xa0, xa1, ha, la) + LX * stage1(a0, a1, hya, lya, xb0, xb1, hb, lb)) +
-                        LY * (HX * stage1(b0, b1, hyb, lyb, xa0, xa1, ha, la) + LX * stage1(b0, b1, hyb, lyb, xb0, xb1, hb, lb));
-                }
+                const ColTaps c = col_taps<SAME>(p.s1x, p.s2x, x, p.wm, p.iw);
+                const float v = resize_value<SAME>(a0, a1, b0, b1, r, c);
                 nib |= (v > 0.f ? 1u : 0u) << j;
             }
             if (++x == p.ow) {
@@ -254,6 +292,158 @@ __global__ __launch_bounds__(256) void pack_bits_kernel(const uint8_t *__restric
     if ((lane & 31) == 0 && w < words) bits[(long)k * words + w] = (uint32_t)(lane ? (b >> 32) : (b & 0xFFFFFFFFull));
 }
 
+// ---- proposal index maps (DAVIS): low-resolution logits -> one label per output pixel, no [K][T][oh][ow] tensor -------------
+//
+// One workgroup of 256 threads owns an IX_TH x IX_TW = 16 x 64 tile of one output frame; a thread owns 4 consecutive pixels of
+// one tile row and writes them as one dword.  The low-resolution window under the tile (rows win_lo(first tile row) ..
+// win_hi(last tile row), the same for columns: src_tap is monotone in dst, so the taps of every pixel of the tile lie inside)
+// is gathered once into LDS as K planes [K][wh*ww] -- only the K selected columns of each 4*ldq-byte logit row -- and the 16 taps
+// x K of every pixel are LDS reads.  Without it every output pixel would do 16 x K scattered global reads; a low-resolution
+// pixel feeds about (oh/hm)^2 output pixels (28 at DAVIS 480p from a 360-pixel test size).
+//
+// Tile, LDS and occupancy: at that size the window is 6 x 15 pixels, at K = 20 7.2 KB (+ 2 KB of query / score).  The two-stage
+// kernel holds the four pixels' column taps in registers (132 VGPRs; 63 for SAME), so three workgroups (12 waves) run per CU,
+// four or eight for SAME: registers, not the 28 KB of LDS those three take of 160 KB, bound occupancy there.  A wider tile would amortise the one-pixel window apron better (the
+// window is (16/5.3 + 3) x (64/5.3 + 3) for 1024 pixels: the apron is a third of it), but 64 is the widest at which a 256-thread
+// workgroup still has 16 rows, and a 4-row wave reads few distinct LDS rows per instruction.  IX_LDS_BYTES = 40 KB is the budget:
+// the three workgroups the registers admit still fit a CU (126 of 160 KB), so a large K costs no occupancy; K * window
+// beyond it (K = 254 over more than 40 window pixels, or a strong downscale) takes the direct path: the same arithmetic on
+// the pixel-major logits themselves, column indices scaled by ldq.  The launcher computes the largest window over all tiles
+// with the same win_lo / win_hi the kernel uses; a workgroup whose own window would still not fit what was allocated (it cannot
+// happen: host and device evaluate the same float32 operations) reads directly instead of past its LDS.
+constexpr int IX_TH = 16, IX_TW = 64, IX_KMAX = 254, IX_LDS_BYTES = 40 * 1024;
+
+template <bool SAME>
+__host__ __device__ __forceinline__ int win_lo(float s1, float s2, int dst, int in_low, int in_mid)
+{
+    int i0, i1; float l0, l1;
+    if (!SAME) { src_tap(s2, dst, in_mid, i0, i1, l0, l1); dst = i0; }
+    src_tap(s1, dst, in_low, i0, i1, l0, l1);
+    return i0;
+}
+
+template <bool SAME>
+__host__ __device__ __forceinline__ int win_hi(float s1, float s2, int dst, int in_low, int in_mid)
+{
+    int i0, i1; float l0, l1;
+    if (!SAME) { src_tap(s2, dst, in_mid, i0, i1, l0, l1); dst = i1; }
+    src_tap(s1, dst, in_low, i0, i1, l0, l1);
+    return i1;
+}
+
+struct IndexParams {
+    const float *ml;           // [T*hm*wm][ldq]
+    const int *query;          // [K]
+    const float *score;        // [K] (rule 1)
+    uint8_t *index;            // [T][oh][ow]
+    int ldq, T, hm, wm, ih, iw, oh, ow, K, rule;
+    int tiles_x, tiles_y;
+    int cap;                   // window pixels the dynamic LDS holds per proposal (0: every workgroup reads directly)
+    float s1y, s1x, s2y, s2x;
+};
+
+template <bool SAME>
+__global__ __launch_bounds__(256) void infer_index_kernel(IndexParams p)
+{
+    extern __shared__ float win[];                      // [K][wh*ww]
+    __shared__ int qs[IX_KMAX];
+    __shared__ float ss[IX_KMAX];
+    const unsigned int per_frame = (unsigned int)p.tiles_x * (unsigned int)p.tiles_y;
+    const int t = (int)(blockIdx.x / per_frame);
+    const unsigned int rem = blockIdx.x - (unsigned int)t * per_frame;
+    const int ty = (int)(rem / (unsigned int)p.tiles_x), tx = (int)(rem - (unsigned int)ty * (unsigned int)p.tiles_x);
+    const int y0 = ty * IX_TH, x0 = tx * IX_TW;
+    const int ylast = (y0 + IX_TH < p.oh ? y0 + IX_TH : p.oh) - 1, xlast = (x0 + IX_TW < p.ow ? x0 + IX_TW : p.ow) - 1;
+    // the window; clamped to the map so that no tap arithmetic, however it rounds, makes the gather read outside the logits
+    const int rlo = win_lo<SAME>(p.s1y, p.s2y, y0, p.hm, p.ih), clo = win_lo<SAME>(p.s1x, p.s2x, x0, p.wm, p.iw);
+    int rhi = win_hi<SAME>(p.s1y, p.s2y, ylast, p.hm, p.ih), chi = win_hi<SAME>(p.s1x, p.s2x, xlast, p.wm, p.iw);
+    if (rhi > p.hm - 1) rhi = p.hm - 1;
+    if (chi > p.wm - 1) chi = p.wm - 1;
+    const int wh = rhi - rlo + 1, ww = chi - clo + 1, np = wh * ww;
+    const bool staged = np >= 1 && np <= p.cap;         // workgroup-uniform
+
+    for (int k = threadIdx.x; k < p.K; k += 256) {
+        int q = p.query[k];
+        q = q < 0 ? 0 : (q > p.ldq - 1 ? p.ldq - 1 : q);
+        qs[k] = q;
+        ss[k] = p.rule ? p.score[k] : 0.f;
+    }
+    __syncthreads();
+    const float *frame = p.ml + (long)t * p.hm * p.wm * p.ldq;
+    if (staged) {
+        for (int idx = threadIdx.x; idx < np * p.K; idx += 256) {
+            const int pp = idx / p.K, k = idx - pp * p.K;
+            const int wr = pp / ww, wc = pp - wr * ww;
+            win[k * np + pp] = frame[((long)(rlo + wr) * p.wm + (clo + wc)) * p.ldq + qs[k]];
+        }
+        __syncthreads();
+    }
+
+    const int y = y0 + (int)(threadIdx.x >> 4), xb = x0 + (int)(threadIdx.x & 15) * 4;
+    if (y >= p.oh || xb >= p.ow) return;
+    const int nx = p.ow - xb < 4 ? p.ow - xb : 4;
+    const RowTaps r = row_taps<SAME>(p.s1y, p.s2y, y, p.hm, p.ih);
+    ColTaps c[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)                         // a column past the frame edge repeats the last one; its label is not stored
+        c[j] = col_taps<SAME>(p.s1x, p.s2x, xb + (j < nx ? j : nx - 1), p.wm, p.iw, staged ? clo : 0, staged ? 1 : p.ldq);
+    // element offsets of the four rows inside one proposal's plane (staged) or inside the frame's logits (direct)
+    const long rs = staged ? (long)ww : (long)p.wm * p.ldq;
+    const int ro = staged ? rlo : 0;
+    const long oa0 = (r.qa0 - ro) * rs, oa1 = (r.qa1 - ro) * rs;
+    const long ob0 = SAME ? 0 : (r.qb0 - ro) * rs, ob1 = SAME ? 0 : (r.qb1 - ro) * rs;
+
+    unsigned int lab[4] = {0u, 0u, 0u, 0u};
+    float best[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < p.K; ++k) {
+        const float *base = staged ? win + k * np : frame + qs[k];
+        const float *a0 = base + oa0, *a1 = base + oa1, *b0 = base + ob0, *b1 = base + ob1;
+        if (p.rule == 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (lab[j] == 0u && resize_value<SAME>(a0, a1, b0, b1, r, c[j]) > 0.f) lab[j] = (unsigned int)k + 1u;
+            if (lab[0] && lab[1] && lab[2] && lab[3]) break;
+        } else {
+            const float s = ss[k];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float v = resize_value<SAME>(a0, a1, b0, b1, r, c[j]);
+                if (v > 0.f) {
+                    const float pr = s / (1.f + expf(-v));
+                    if (lab[j] == 0u || pr > best[j]) { lab[j] = (unsigned int)k + 1u; best[j] = pr; }
+                }
+            }
+        }
+    }
+    uint8_t *o = p.index + ((long)t * p.oh + y) * p.ow + xb;
+    if (nx == 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0)
+        *reinterpret_cast<uint32_t *>(o) = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
+    else
+        for (int j = 0; j < nx; ++j) o[j] = (uint8_t)lab[j];
+}
+
+// largest window (pixels) of any tile, from the same tap functions the kernel evaluates
+template <bool SAME>
+long index_max_window(const IndexParams &p)
+{
+    int mh = 0, mw = 0;
+    for (int ty = 0; ty < p.tiles_y; ++ty) {
+        const int ylast = (ty * IX_TH + IX_TH < p.oh ? ty * IX_TH + IX_TH : p.oh) - 1;
+        int hi = win_hi<SAME>(p.s1y, p.s2y, ylast, p.hm, p.ih);
+        if (hi > p.hm - 1) hi = p.hm - 1;
+        const int h = hi - win_lo<SAME>(p.s1y, p.s2y, ty * IX_TH, p.hm, p.ih) + 1;
+        if (h > mh) mh = h;
+    }
+    for (int tx = 0; tx < p.tiles_x; ++tx) {
+        const int xlast = (tx * IX_TW + IX_TW < p.ow ? tx * IX_TW + IX_TW : p.ow) - 1;
+        int hi = win_hi<SAME>(p.s1x, p.s2x, xlast, p.wm, p.iw);
+        if (hi > p.wm - 1) hi = p.wm - 1;
+        const int w = hi - win_lo<SAME>(p.s1x, p.s2x, tx * IX_TW, p.wm, p.iw) + 1;
+        if (w > mw) mw = w;
+    }
+    return (long)mh * mw;
+}
+
 }  // namespace
 
 extern "C" {
@@ -303,6 +493,44 @@ int s2d_infer_masks_u8(const float *mask_logits, int ldq, int T, int hm, int wm,
     const long nthreads = (p.words * 32 + 3) / 4;       // whole words: the tail lanes write the zero padding bits
     if (p.same) hipLaunchKernelGGL(infer_resize_kernel<true>, dim3(cdiv(nthreads, 256), K), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(infer_resize_kernel<false>, dim3(cdiv(nthreads, 256), K), dim3(256), 0, stream, p);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+// geometry of one s2d_infer_index_u8 call -> p (pointers and rule left alone); false: the sizes are refused
+static bool index_geometry(IndexParams &p, int ldq, int T, int hm, int wm, int Hp, int Wp, int ih, int iw, int oh, int ow, int K)
+{
+    if (K < 1 || K > IX_KMAX || ldq < 4 || ldq > 128 || (ldq & 3)) return false;
+    if (T < 1 || hm < 1 || wm < 1 || ih < 1 || iw < 1 || ih > Hp || iw > Wp || oh < 1 || ow < 1) return false;
+    if ((long)hm * wm * ldq > 0x7FFFFFFFL) return false;
+    p.ldq = ldq; p.T = T; p.hm = hm; p.wm = wm; p.ih = ih; p.iw = iw; p.oh = oh; p.ow = ow; p.K = K;
+    p.tiles_x = cdiv(ow, IX_TW); p.tiles_y = cdiv(oh, IX_TH);
+    if ((long)T * p.tiles_x * p.tiles_y >= (1L << 31)) return false;
+    p.s1y = (float)hm / Hp; p.s1x = (float)wm / Wp; p.s2y = (float)ih / oh; p.s2x = (float)iw / ow;
+    const long maxwin = (ih == oh && iw == ow) ? index_max_window<true>(p) : index_max_window<false>(p);
+    p.cap = (maxwin >= 1 && maxwin * K * (long)sizeof(float) <= IX_LDS_BYTES) ? (int)maxwin : 0;
+    return true;
+}
+
+long s2d_infer_index_lds_bytes(int ldq, int T, int hm, int wm, int Hp, int Wp, int ih, int iw, int oh, int ow, int K)
+{
+    IndexParams p;
+    if (!index_geometry(p, ldq, T, hm, wm, Hp, Wp, ih, iw, oh, ow, K)) return -1;
+    return (long)p.cap * K * (long)sizeof(float);
+}
+
+int s2d_infer_index_u8(const float *mask_logits, int ldq, int T, int hm, int wm, int Hp, int Wp, int ih, int iw, int oh, int ow,
+                       const int *query, const float *score, int K, int rule, uint8_t *index, hipStream_t stream)
+{
+    if (!mask_logits || !query || !index || (rule != 0 && rule != 1) || (rule == 1 && !score)) return S2D_ERR_ARG;
+    IndexParams p;
+    if (!index_geometry(p, ldq, T, hm, wm, Hp, Wp, ih, iw, oh, ow, K)) return S2D_ERR_ARG;
+    p.ml = mask_logits; p.query = query; p.score = score; p.index = index; p.rule = rule;
+    const bool same = ih == oh && iw == ow;
+    const long nblocks = (long)T * p.tiles_x * p.tiles_y;
+    const size_t lds = (size_t)p.cap * K * sizeof(float);
+    if (same) hipLaunchKernelGGL(infer_index_kernel<true>, dim3((unsigned int)nblocks), dim3(256), lds, stream, p);
+    else hipLaunchKernelGGL(infer_index_kernel<false>, dim3((unsigned int)nblocks), dim3(256), lds, stream, p);
     S2D_CHECK_LAUNCH();
     return S2D_OK;
 }

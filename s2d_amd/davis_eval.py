@@ -336,6 +336,139 @@ def evaluate_davis(gt_dir, results_dir, *, sequences=None, task="unsupervised", 
     return {"global": table, "per_sequence": rows, "sequences": per}
 
 
+# --------------------------------------------------------------------------------------------------------------- palette, writing
+def _voc_colour(i):
+    """entry i of the PASCAL-VOC colour map: for j = 0..7, bits 3j, 3j + 1, 3j + 2 of i become bit 7 - j of r, g, b"""
+    r = g = b = 0
+    for j in range(8):
+        r |= ((i >> 0) & 1) << (7 - j)
+        g |= ((i >> 1) & 1) << (7 - j)
+        b |= ((i >> 2) & 1) << (7 - j)
+        i >>= 3
+    return [r, g, b]
+
+
+# 256 entries: the first 13 are the demo's PALETTE (what its mask PNGs carry; they differ from the formula by 191 for 192), the
+# rest the VOC formula, so that all 20 proposals of the unsupervised protocol -- and any label up to 255 -- have a colour
+DAVIS_PALETTE = [0, 0, 0, 128, 0, 0, 0, 128, 0, 128, 128, 0, 0, 0, 128, 128, 0, 128, 0, 128, 128, 128, 128, 128, 64, 0, 0, 191, 0, 0,
+                 64, 128, 0, 191, 128, 0, 64, 0, 128] + [c for i in range(13, 256) for c in _voc_colour(i)]
+
+
+def save_index_png(path, index):
+    """uint8 index map [H, W] -> a P-mode PNG with DAVIS_PALETTE (read_index_png reads the labels back)"""
+    from PIL import Image
+    index = np.ascontiguousarray(index)
+    if index.dtype != np.uint8 or index.ndim != 2:
+        raise ValueError(f"{path}: an index map is uint8 [H, W], not {index.dtype} {index.shape}")
+    im = Image.fromarray(index)
+    im.putpalette(DAVIS_PALETTE)                                        # an L image with a palette is saved in mode P
+    im.save(path)
+
+
+# --------------------------------------------------------------------------------------------------------------- driver side
+def merge_sequence_results(parts, names):
+    """parts: per rank, a list of (sequence name, sequence_metrics result) -> OrderedDict in the order of `names`.  A sequence
+    scored twice or not at all, or one that is not in the list, is an error: the ranks split the list, nothing else"""
+    got = {}
+    for part in parts:
+        for name, r in part:
+            if name in got:
+                raise ValueError(f"sequence {name} was scored by more than one rank")
+            got[name] = r
+    extra = sorted(set(got) - set(names))
+    if extra:
+        raise ValueError(f"results for sequences the list does not have: {extra}")
+    missing = [n for n in names if n not in got]
+    if missing:
+        raise ValueError(f"no result for sequences {missing}")
+    return OrderedDict((n, got[n]) for n in names)
+
+
+class DAVISEvaluator:
+    """reset / process(inputs, outputs) / evaluate() on the proposal index maps a model returns (`inference_index`,
+    modeling/postprocess.inference_video index_map=...): `process` reads the sequence's ground-truth PNGs and scores the CUDA index
+    tensor where it is (sequence_metrics), and queues the PNGs output_dir/davis/<sequence>/<frame>.png to a small thread pool;
+    evaluate() gathers the per-sequence results of all ranks, orders them by the sequence list, writes global_results.csv and
+    per-sequence_results.csv and returns {"davis": the global table}.  Only the unsupervised task: the model takes no first-frame
+    mask.  PARITY WITH THE DAVIS TOOLKIT IS UNPINNED (module docstring)."""
+
+    def __init__(self, gt_dir, output_dir=None, task="unsupervised", bound_th=0.008, max_proposals=20, distributed=True, sequences=None,
+                 threads=4, video_names=None):
+        if task not in TASKS:
+            raise ValueError(f"task {task!r}: one of {TASKS}")
+        if task != "unsupervised":
+            raise ValueError("the semi-supervised task needs a first-frame mask, which the model does not take: DAVISEvaluator scores "
+                             "the unsupervised task (a folder of semi-supervised results: python -m s2d_amd.davis_eval --task semi-supervised)")
+        if not 1 <= int(threads) <= 16:
+            raise ValueError("threads must be in [1, 16]")
+        self._gt_dir, self._output_dir, self._distributed = gt_dir, output_dir, distributed
+        self._bound_th, self._max_proposals, self._threads = bound_th, int(max_proposals), int(threads)
+        self._names = _sequence_names(gt_dir, sequences)
+        self._video_names = dict(video_names or {})                     # video_id -> sequence name (davis_video_document's records)
+        self._pool, self._writes = None, []
+        self.reset()
+
+    def reset(self):
+        self._drain()
+        self._results = []
+
+    def _drain(self):
+        for fu in self._writes:
+            fu.result()                                                 # a failed write raises here
+        self._writes = []
+        if self._pool is not None:
+            self._pool.shutdown()
+            self._pool = None
+
+    def process(self, inputs, outputs):
+        """inputs: one video of the test loader over davis_video_document (`name`, `file_names`); outputs: inference_video's dict with
+        "pred_masks_format": "index_u8" """
+        assert len(inputs) == 1, "More than one inputs are loaded for inference!"
+        video = inputs[0]
+        out = outputs[0] if isinstance(outputs, (list, tuple)) else outputs
+        if out.get("pred_masks_format") != "index_u8":
+            raise ValueError("DAVISEvaluator scores proposal index maps: set the model's inference_index (pred_masks_format 'index_u8')")
+        # the loader's records carry video_id and file_names: the sequence is the id's name in the document, else the frames' folder
+        name = video.get("name") or self._video_names.get(video.get("video_id")) or os.path.basename(os.path.dirname(video["file_names"][0]))
+        if name not in self._names:
+            raise ValueError(f"sequence {name} is not in the sequence list")
+        stems = [os.path.splitext(os.path.basename(f))[0] for f in video["file_names"]]
+        gt = _read_video(self._gt_dir, name, [s + ".png" for s in stems])
+        index = out["pred_masks"]
+        if tuple(index.shape) != gt.shape:
+            raise ValueError(f"sequence {name}: index maps {tuple(index.shape)}, ground truth {gt.shape}")
+        r = sequence_metrics(gt, index, task="unsupervised", bound_th=self._bound_th, max_proposals=self._max_proposals,
+                             device=index.device)
+        self._results.append((name, r))
+        if self._output_dir:
+            from concurrent.futures import ThreadPoolExecutor
+            if self._pool is None:
+                self._pool = ThreadPoolExecutor(self._threads)
+            sdir = os.path.join(self._output_dir, "davis", name)
+            os.makedirs(sdir, exist_ok=True)
+            host = index.cpu().numpy()
+            self._writes += [self._pool.submit(save_index_png, os.path.join(sdir, s + ".png"), host[t]) for t, s in enumerate(stems)]
+
+    def evaluate(self):
+        self._drain()
+        parts = [self._results]
+        try:
+            import torch.distributed as dist
+            if self._distributed and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                parts = [None] * dist.get_world_size()
+                dist.all_gather_object(parts, self._results)
+                if dist.get_rank() != 0:
+                    return {}
+        except ImportError:
+            pass
+        per = merge_sequence_results(parts, self._names)
+        table, rows = tables(per)
+        self.result = {"global": table, "per_sequence": rows, "sequences": per}
+        if self._output_dir:
+            write_csvs(self.result, self._output_dir)
+        return {"davis": dict(table)}
+
+
 # --------------------------------------------------------------------------------------------------------------- CLI
 def format_table(table):
     keys = list(table)

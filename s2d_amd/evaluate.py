@@ -19,7 +19,17 @@ the same `model([inputs])` (data/coco_image_loader.COCOImageTestLoader, coco_eva
 OUT/coco_instances_results.json and OUT/metrics.json as {"segm": ..., "bbox": ...} (mask AP and box AP of the masks' tight boxes,
 12 metrics each); the timing line counts `images`.  --iou-types segm,bbox[,boundary] (image format only; default segm,bbox) chooses
 the dicts of metrics.json: `boundary` adds Boundary AP (coco_eval.py), bands --dilation-ratio of the image diagonal wide.
---boundary-ap is a YTVIS option: with the image format it is refused (--iou-types is the image format's switch)."""
+--boundary-ap is a YTVIS option: with the image format it is refused (--iou-types is the image format's switch).
+
+--test-format davis (auto: --gt is a directory): DAVIS-2017 unsupervised J&F of the checkpoint.  --gt is the annotation directory
+(Annotations_unsupervised/480p), --image-root is JPEGImages/480p, --sequences a text file of sequence names (default: every
+sub-directory of --gt).  Every sequence runs through the same `model([inputs])` with the model's inference_index switch: the
+proposals (--max-proposals of at most 254, default 20, scored --score-threshold or better) become one non-overlapping index map
+per frame on the device (ops.infer_index; --index-rule rank: a pixel goes to its best-ranked proposal; prob: to the largest
+score * sigmoid(logit)), which davis_eval.DAVISEvaluator scores where it is (--bound-th: the F-measure's boundary tolerance) and
+writes as OUT/davis/<sequence>/<frame>.png.  OUT/global_results.csv, OUT/per-sequence_results.csv, OUT/metrics.json =
+{"davis": {...}}; the timing line counts `videos`.  --boundary-ap and --iou-types are refused.  Parity with the DAVIS toolkit is
+unpinned (davis_eval.py)."""
 import argparse
 import json
 import os
@@ -27,6 +37,9 @@ import sys
 import time
 
 import torch
+
+
+TEST_FORMATS = ("auto", "ytvis", "coco_image", "davis")
 
 
 def parse_args(argv=None):
@@ -42,8 +55,14 @@ def parse_args(argv=None):
     ap.add_argument("--boundary-ap", action="store_true", help="also score Boundary AP (matching on min(mask IoU, boundary IoU))")
     ap.add_argument("--dilation-ratio", type=float, default=0.02, help="boundary band width as a fraction of the image diagonal")
     ap.add_argument("--iou-types", default=None, help="image format only: comma-separated list of segm, bbox, boundary (default segm,bbox)")
-    ap.add_argument("--test-format", choices=("auto", "ytvis", "coco_image"), default="auto",
-                    help="the --gt document: YTVIS videos or COCO images (auto: `images` without `videos` is coco_image)")
+    ap.add_argument("--test-format", choices=TEST_FORMATS, default="auto",
+                    help="the --gt document: YTVIS videos, COCO images or a DAVIS annotation directory (auto: a directory is davis, "
+                         "`images` without `videos` is coco_image)")
+    ap.add_argument("--sequences", default=None, help="davis: text file of sequence names (default: every sub-directory of --gt)")
+    ap.add_argument("--index-rule", choices=("rank", "prob"), default="rank", help="davis: which proposal takes a contested pixel")
+    ap.add_argument("--max-proposals", type=int, default=20, help="davis: proposals per sequence (<= 254)")
+    ap.add_argument("--score-threshold", type=float, default=0.0, help="davis: proposals scored below it are dropped")
+    ap.add_argument("--bound-th", type=float, default=0.008, help="davis: boundary tolerance of the F-measure")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="config overrides KEY VALUE ...")
     return ap.parse_args(argv)
 
@@ -79,11 +98,24 @@ def parse_iou_types(text):
 
 
 def resolve_test_format(fmt, doc, boundary=False, iou_types=None):
-    """--test-format -> "ytvis" or "coco_image" for the loaded --gt document; --boundary-ap with the image format is refused, and
-    so is --iou-types (anything but None) with the YTVIS format"""
+    """--test-format -> "ytvis", "coco_image" or "davis" for the loaded --gt document (davis: the annotation directory's path);
+    --boundary-ap with the image format is refused, and so is --iou-types (anything but None) with the YTVIS format; the DAVIS
+    format refuses both"""
     from .data.image_clip import detect_train_format
-    if fmt not in ("auto", "ytvis", "coco_image"):
-        raise ValueError(f"test format {fmt!r}: auto, ytvis or coco_image")
+    if fmt not in TEST_FORMATS:
+        raise ValueError(f"test format {fmt!r}: auto, ytvis, coco_image or davis")
+    is_dir = isinstance(doc, (str, os.PathLike)) and os.path.isdir(doc)
+    if fmt == "davis" or (fmt == "auto" and is_dir):
+        if not is_dir:
+            raise ValueError("--test-format davis scores against an annotation directory (Annotations_unsupervised/480p): --gt is not one")
+        if boundary:
+            raise ValueError("--boundary-ap scores YTVIS videos: it is not available with --test-format davis "
+                             "(the F-measure is DAVIS' boundary score; its tolerance: --bound-th)")
+        if iou_types is not None:
+            raise ValueError("--iou-types chooses the tables of a COCO image split: it is not available with --test-format davis")
+        return "davis"
+    if is_dir:
+        raise ValueError(f"--test-format {fmt} reads an annotation JSON: --gt is a directory (a DAVIS tree: --test-format davis)")
     fmt = detect_train_format(doc) if fmt == "auto" else fmt
     if fmt == "coco_image" and boundary:
         raise ValueError("--boundary-ap scores YTVIS videos: it is not available with --test-format coco_image "
@@ -95,26 +127,47 @@ def resolve_test_format(fmt, doc, boundary=False, iou_types=None):
 
 
 def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, prefetch=2, boundary=False, dilation_ratio=0.02,
-                   test_format="ytvis", iou_types=None):
+                   test_format="ytvis", iou_types=None, davis=None):
     """score `model` on a YTVIS split: every video through `model([inputs])` (eval mode, predictions as COCO RLE) with the test
     loader and YTVISEvaluator; writes output_dir/results.json and, on rank 0 of a split with annotations, output_dir/metrics.json
     (boundary: Boundary AP as well, and metrics.json holds {"segm", "boundary"}).
     test_format "coco_image" ("auto": decided by the document): a COCO image split instead -- COCOImageTestLoader and
     COCOImageEvaluator, files output_dir/coco_instances_results.json and metrics.json = {"segm", "bbox"}, `images` in the timing line;
     iou_types (image format only; None: ("segm", "bbox")) chooses those dicts, "boundary" among them.
-    The model's training mode and inference_rle switch are restored afterwards.  -> (results, timing line dict)"""
+    A directory as `gt` (test_format "davis" or "auto"): a DAVIS tree -- davis_video_document, the model's inference_index switch and
+    DAVISEvaluator; `davis` = {"sequences", "rule", "max_proposals", "score_threshold", "bound_th"} (defaults: every sequence, "rank",
+    20, 0.0, 0.008); files output_dir/davis/<sequence>/<frame>.png, the two CSVs and metrics.json = {"davis": the global table}.
+    The model's training mode and inference switches are restored afterwards.  -> (results, timing line dict)"""
     from .data.test_loader import YTVISTestLoader
     from .ytvis_eval import YTVISEvaluator
     import torch.distributed as dist
     rank = dist.get_rank() if dist.is_initialized() else 0
+    is_davis = isinstance(gt, (str, os.PathLike)) and os.path.isdir(gt) and \
+        resolve_test_format(test_format, gt, boundary, iou_types) == "davis"
+    index_map = None
+    if is_davis:
+        from .data.davis_loader import davis_video_document
+        opt = {"sequences": None, "rule": "rank", "max_proposals": 20, "score_threshold": 0.0, "bound_th": 0.008, **(davis or {})}
+        gt_dir, gt = gt, davis_video_document(image_root, gt, opt["sequences"])     # refuses a broken tree before the model runs
+        index_map = {"rule": opt["rule"], "max_proposals": opt["max_proposals"], "score_threshold": opt["score_threshold"]}
+    elif test_format == "davis":
+        resolve_test_format(test_format, gt, boundary, iou_types)                    # raises: not a directory
     if isinstance(gt, str):
         with open(gt) as fh:
             gt = json.load(fh)
     # labels -> dataset category ids as the registered dataset's metadata maps them (load_ytvis_json: sorted ids, contiguous)
     id_map = {c: i for i, c in enumerate(sorted(c["id"] for c in gt.get("categories", [])))} or None
-    images = resolve_test_format(test_format, gt, boundary, iou_types) == "coco_image"
+    images = not is_davis and resolve_test_format(test_format, gt, boundary, iou_types) == "coco_image"
     iou_types = parse_iou_types(iou_types)
-    if images:
+    if is_davis:
+        from .davis_eval import DAVISEvaluator
+        from .modeling.postprocess import index_map_options
+        index_map_options(index_map)
+        evaluator = DAVISEvaluator(gt_dir, output_dir, bound_th=opt["bound_th"], max_proposals=opt["max_proposals"], distributed=True,
+                                   sequences=[v["name"] for v in gt["videos"]], threads=min(max(int(threads), 1), 16),
+                                   video_names={v["id"]: v["name"] for v in gt["videos"]})
+        loader = YTVISTestLoader.from_config(cfg, gt, image_root, device=device, threads=threads, prefetch=prefetch)
+    elif images:
         from .coco_eval import COCOImageEvaluator
         from .data.coco_image_loader import COCOImageTestLoader
         evaluator = COCOImageEvaluator(json_file=gt, distributed=True, output_dir=output_dir, dataset_id_to_contiguous_id=id_map,
@@ -126,9 +179,10 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
         loader = YTVISTestLoader.from_config(cfg, gt, image_root, device=device, threads=threads, prefetch=prefetch)
     evaluator.reset()
 
-    was_training, was_rle = model.training, getattr(model, "inference_rle", False)
+    was_training, was_rle, was_index = model.training, getattr(model, "inference_rle", False), getattr(model, "inference_index", None)
     model.eval()
-    model.inference_rle = True
+    model.inference_rle = not is_davis
+    model.inference_index = index_map
     nvid = nfr = nwin = 0
     try:
         torch.cuda.synchronize(device)
@@ -145,11 +199,15 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
     finally:
         model.train(was_training)
         model.inference_rle = was_rle
+        model.inference_index = was_index
 
     results = evaluator.evaluate()
     if rank == 0:
         os.makedirs(output_dir, exist_ok=True)
-        if images and results:
+        if is_davis and results:
+            with open(os.path.join(output_dir, "metrics.json"), "w") as fh:
+                json.dump(results, fh)
+        elif images and results:
             with open(os.path.join(output_dir, "metrics.json"), "w") as fh:
                 json.dump({k: results[k] for k in iou_types}, fh)
         elif "segm" in results:
@@ -174,13 +232,25 @@ def main(argv=None):
     torch.cuda.set_device(device)
 
     cfg = load_config(a.config_file, a.opts)
-    with open(a.gt) as fh:
-        gt_doc = json.load(fh)
     iou_types = parse_iou_types(a.iou_types) if a.iou_types is not None else None
+    davis = None
+    if os.path.isdir(a.gt) or a.test_format == "davis":
+        gt_doc = a.gt                                                   # the annotation directory; evaluate_model lists it
+        davis = {"sequences": a.sequences, "rule": a.index_rule, "max_proposals": a.max_proposals,
+                 "score_threshold": a.score_threshold, "bound_th": a.bound_th}
+    else:
+        with open(a.gt) as fh:
+            gt_doc = json.load(fh)
     fmt = resolve_test_format(a.test_format, gt_doc, a.boundary_ap, iou_types)
+    if fmt == "davis":                                                  # a broken tree is refused before the model is built
+        from .data.davis_loader import davis_video_document
+        from .modeling.postprocess import index_map_options
+        index_map_options({"rule": a.index_rule, "max_proposals": a.max_proposals, "score_threshold": a.score_threshold})
+        davis_video_document(a.image_root, a.gt, a.sequences)
     model = build_model(cfg, a.weights or cfg.MODEL.WEIGHTS, device)
     results, line = evaluate_model(cfg, model, gt_doc, a.image_root, a.output_dir, device, a.threads, a.prefetch,
-                                   boundary=a.boundary_ap, dilation_ratio=a.dilation_ratio, test_format=fmt, iou_types=iou_types)
+                                   boundary=a.boundary_ap, dilation_ratio=a.dilation_ratio, test_format=fmt, iou_types=iou_types,
+                                   davis=davis)
     print(json.dumps(line), flush=True)
     if dist.is_initialized():
         dist.barrier()

@@ -264,6 +264,7 @@ class KDVideoMaskFormer(nn.Module):
         self.overlap_teacher, self._side = False, None
         self.inference_rle = False                  # eval branch: pred_masks as COCO RLE lists encoded on the device (inference_video rle=True)
         self.inference_device_masks = False         # eval branch: pred_masks as the CUDA u8 [K,T,H,W] tensor (inference_video device_masks=True)
+        self.inference_index = None                 # eval branch: a dict -> pred_masks as ONE CUDA u8 [T,H,W] proposal index map (inference_video index_map=...)
         self._side_delay_cycles = 0                 # tests only: spin the side stream this many cycles before the GT criterion
 
     @classmethod
@@ -638,14 +639,14 @@ class KDVideoMaskFormer(nn.Module):
         net = self.student if self.eval_student else self.teacher
         return _inference(net, images, batched_inputs, self.num_predictions_inference, self.use_nms, self.nms_threshold,
                           rle=getattr(self, "inference_rle", False), device_masks=getattr(self, "inference_device_masks", False),
-                          window=self._window(), owner=self)
+                          window=self._window(), owner=self, index_map=getattr(self, "inference_index", None))
 
     def _window(self):
         return (self.window_size, self.window_overlap) if self.window_inference else None
 
 
 def _inference(net, images, batched_inputs, num_predictions, use_nms, nms_threshold, rle=False, device_masks=False, window=None,
-               owner=None):
+               owner=None, index_map=None):
     """window = (W, O): a video of more than W frames runs window by window and is stitched (window_inference.run_windows); one of
     at most W frames, or window = None, is the one-clip path.  owner.last_windows receives the number of windows run."""
     video = batched_inputs[0]
@@ -665,7 +666,7 @@ def _inference(net, images, batched_inputs, num_predictions, use_nms, nms_thresh
     height, width = video.get("height", image_size[0]), video.get("width", image_size[1])   # :351-352
     return inference_video(cls, ml, dims, tuple(images.shape[1:3]),
                            image_size, (int(height), int(width)), num_predictions, use_nms, nms_threshold, rle=rle,
-                           device_masks=device_masks)
+                           device_masks=device_masks, index_map=index_map)
 
 
 @META_ARCH_REGISTRY.register()
@@ -684,6 +685,7 @@ class VideoMaskFormer(nn.Module):
         self.register_buffer("pixel_std", torch.tensor(pixel_std, dtype=torch.float32).view(-1, 1, 1), False)
         self.inference_rle = False                  # see KDVideoMaskFormer
         self.inference_device_masks = False
+        self.inference_index = None
         self.window_inference, self.window_size, self.window_overlap = bool(window_inference), int(window_size), int(window_overlap)
         self.last_windows = 0
 
@@ -772,7 +774,8 @@ class VideoMaskFormer(nn.Module):
                 return _inference(net, images, batched_inputs, self.num_predictions, self.use_nms, self.nms_threshold,
                                   rle=getattr(self, "inference_rle", False),
                                   device_masks=getattr(self, "inference_device_masks", False),
-                                  window=(self.window_size, self.window_overlap) if self.window_inference else None, owner=self)
+                                  window=(self.window_size, self.window_overlap) if self.window_inference else None, owner=self,
+                                  index_map=getattr(self, "inference_index", None))
         Hp, Wp = images.shape[1:3]
         gt = TargetSet.from_list(_gt_target_list(batched_inputs, self.num_frames, Hp, Wp, self.device), device=self.device)
         params = [p for p in list(self.backbone.parameters()) + list(self.sem_seg_head.parameters()) if p.requires_grad]

@@ -34,15 +34,64 @@ def greedy_mask_nms(inter, labels, thr):
     return keep
 
 
+def index_map_options(index_map):
+    """{"rule", "max_proposals", "score_threshold"} with the defaults ("rank", 20, 0.0) filled in; unknown keys, rules and proposal
+    counts outside 1..254 are refused"""
+    opts = {"rule": "rank", "max_proposals": 20, "score_threshold": 0.0}
+    unknown = set(index_map) - set(opts)
+    if unknown:
+        raise ValueError(f"index_map keys {sorted(unknown)}: rule, max_proposals and score_threshold are known")
+    opts.update(index_map)
+    if opts["rule"] not in ops.INDEX_RULES:
+        raise ValueError(f"index_map rule {opts['rule']!r}: one of {', '.join(ops.INDEX_RULES)}")
+    if not 1 <= int(opts["max_proposals"]) <= ops.INDEX_MAX_PROPOSALS:
+        raise ValueError(f"index_map max_proposals = {opts['max_proposals']}: 1..{ops.INDEX_MAX_PROPOSALS} (label 255 is void)")
+    return opts["rule"], int(opts["max_proposals"]), float(opts["score_threshold"])
+
+
+def _inference_index(class_logits, mask_logits, dims, padded, img_size, out_size, num_predictions, use_nms, nms_threshold, index_map):
+    """inference_video(index_map=...): the proposals are infer_select's top num_predictions, without those scored below the
+    threshold, (use_nms) without those the greedy mask-NMS suppresses -- the only step that still needs bit planes, of the
+    thresholded candidates -- and of the rest the first max_proposals; label p + 1 of the map is pred_scores[p]"""
+    rule, max_proposals, threshold = index_map_options(index_map)
+    T = dims[0]
+    dev = mask_logits.device
+    sel = []
+    if class_logits.shape[0]:
+        scores, query, label = ops.infer_select(class_logits, num_predictions)
+        n = int((~(scores < threshold)).sum())                       # the scores descend: a prefix
+        sel = list(range(n))
+        if use_nms and n:
+            _, bits = ops.infer_masks(mask_logits, dims, padded, img_size, out_size, query[:n].contiguous(), want_bits=True)
+            sel = greedy_mask_nms(ops.mask_pair_counts(bits).cpu().numpy(), label[:n].cpu().numpy(), nms_threshold)
+        sel = sel[:max_proposals]
+    if not sel:
+        index = torch.zeros((T,) + tuple(out_size), device=dev, dtype=torch.uint8)
+        return {"image_size": tuple(out_size), "pred_scores": [], "pred_labels": [], "pred_masks": index, "pred_masks_format": "index_u8"}
+    idx = torch.as_tensor(sel, device=dev, dtype=torch.long)
+    scores, query, label = scores[idx].contiguous(), query[idx].contiguous(), label[idx]
+    index = ops.infer_index(mask_logits, dims, padded, img_size, out_size, query, scores, rule)
+    return {"image_size": tuple(out_size), "pred_scores": scores.tolist(), "pred_labels": label.tolist(), "pred_masks": index,
+            "pred_masks_format": "index_u8"}
+
+
 @torch.no_grad()
 def inference_video(class_logits, mask_logits, dims, padded, img_size, out_size, num_predictions, use_nms=False,
-                    nms_threshold=0.75, rle=False, device_masks=False):
+                    nms_threshold=0.75, rle=False, device_masks=False, index_map=None):
     """class_logits [Q,C+1]; mask_logits pixel-major [T*hm*wm, ldq] of ONE video; dims = (T, hm, wm); padded = network
     input size (Hp,Wp), img_size = size without padding, out_size = (height, width) of the original video.
     Returns the reference's dict: image_size, pred_scores (list of float), pred_labels (list of int), pred_masks (list of
     CPU bool tensors [T,H,W]).  rle=True: the masks stay on the device and `pred_masks` holds, per prediction, the list of T
     COCO RLE dicts that instances_to_coco_json_video (data_video/ytvis_eval.py:345-350) would build from them.
-    device_masks=True: `pred_masks` is the CUDA u8 tensor [K,T,H,W] (0 / 1, after NMS) with "pred_masks_format": "device_u8"."""
+    device_masks=True: `pred_masks` is the CUDA u8 tensor [K,T,H,W] (0 / 1, after NMS) with "pred_masks_format": "device_u8".
+    index_map={"rule": "rank" | "prob", "max_proposals": 20, "score_threshold": 0.0}: `pred_masks` is ONE CUDA u8 tensor [T,H,W]
+    of non-overlapping proposal labels (0: none, p + 1: the proposal of pred_scores[p]; ops.infer_index), "pred_masks_format":
+    "index_u8"; not together with rle / device_masks."""
+    if index_map is not None:
+        if rle or device_masks:
+            raise ValueError("index_map replaces pred_masks by one label map: it does not combine with rle / device_masks")
+        return _inference_index(class_logits, mask_logits, dims, padded, img_size, out_size, num_predictions, use_nms, nms_threshold,
+                                index_map)
     if class_logits.shape[0] == 0:                                   # :584-587
         return {"image_size": tuple(out_size), "pred_scores": [], "pred_labels": [], "pred_masks": []}
     scores, query, label = ops.infer_select(class_logits, num_predictions)

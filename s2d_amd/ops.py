@@ -756,6 +756,10 @@ def infer_masks(mask_logits, dims, padded, img_size, out_size, query, want_bits=
     return masks, bits
 
 
+# proposal index maps (s2d_infer_index_u8): defined in index_map.py, re-exported here as ops.infer_index
+from .index_map import INDEX_MAX_PROPOSALS, INDEX_RULES, infer_index  # noqa: E402,F401
+
+
 def pack_mask_bits(masks):
     """u8 masks [K, ...] (0 / non-0) -> int32 bit words [K, ceil(n/32)], the layout mask_pair_counts reads"""
     _chk(masks, torch.uint8)

@@ -26,7 +26,8 @@ continues at iteration + 1; with SEED < 0 it also reuses the saved sampler seed,
 uninterrupted run would (with SEED >= 0 the config's seed is used).
 With --eval-gt the model is scored (evaluate.evaluate_model) every TEST.EVAL_PERIOD iterations and after the last one, into
 OUT/inference/.  An --eval-gt document with `images` and no `videos` is scored as COCO images (coco_eval.COCOImageEvaluator: mask
-AP and box AP, OUT/inference/metrics.json = {"segm", "bbox"}); a YTVIS document as before.
+AP and box AP, OUT/inference/metrics.json = {"segm", "bbox"}); a YTVIS document as before; a directory is a DAVIS annotation tree
+(--eval-image-root: JPEGImages/480p; evaluate.py --test-format davis with its defaults, metrics.json = {"davis"}).
 
 Not supported (refused): INPUT.DISENTANGLE_DISTILLATION_LOADER (the meta-archs take no distill_image) and optimizers other than
 ADAMW.  SOLVER.AMP.ENABLED is ignored with a message: the arithmetic is fp32-class, as in evaluate.py."""
@@ -59,7 +60,7 @@ def parse_args(argv=None):
     ap.add_argument("--output-dir", required=True)
     ap.add_argument("--weights", default=None, help="initial weights, torch .pth or detectron2 .pkl (default: MODEL.WEIGHTS)")
     ap.add_argument("--resume", action="store_true", help="continue from OUTPUT_DIR/last_checkpoint")
-    ap.add_argument("--eval-gt", default=None, help="YTVIS or COCO image annotation JSON to score on (EvalHook)")
+    ap.add_argument("--eval-gt", default=None, help="YTVIS or COCO image annotation JSON, or a DAVIS annotation directory, to score on (EvalHook)")
     ap.add_argument("--eval-image-root", default=None)
     ap.add_argument("--threads", type=int, default=8, help="JPEG decode threads (<= 16)")
     ap.add_argument("--prefetch", type=int, default=2, help="batches prepared ahead")
@@ -248,7 +249,7 @@ def main(argv=None):
             out = os.path.join(a.output_dir, "inference")
             results, line = evaluate_model(cfg, model, a.eval_gt, a.eval_image_root, out, device, a.threads, test_format="auto")
             if rank == 0:
-                print(json.dumps({"eval_iteration": it, **line, **{k: results[k] for k in ("segm", "bbox") if k in results}}),
+                print(json.dumps({"eval_iteration": it, **line, **{k: results[k] for k in ("segm", "bbox", "davis") if k in results}}),
                       flush=True)
 
     hist, names = [], None
