@@ -869,8 +869,9 @@ int s2d_video_grey_u8(const float *video, int T, int H, int W, uint8_t *grey, hi
  * cost is sum |Tm[j][i] - grey[t][c.y + dy + j][c.x + dx + i]|, the best one is the minimum of (cost, dx^2 + dy^2, dy, dx) taken
  * lexicographically, and the point is visible iff cost <= tau (2R+1)^2; visible: c += (dx, dy); not visible: c stays, so a lost
  * point keeps searching round its last good position; tracks[t] = c, vis[t] = visible.  backward != 0: the same from c = p for
- * t = q-1 .. 0; otherwise frames t < q hold p with vis = 0.  One wave per (point, direction); no input makes the kernel read
- * outside grey.  1 <= R <= 7, 1 <= S <= 24, 0 <= tau <= 255, 0 <= q < T, H and W < 2^15; anything else returns S2D_ERR_ARG. */
+ * t = q-1 .. 0; otherwise frames t < q hold p with vis = 0.  It is computed by the search of s2d_block_track_live_u8 with
+ * tau_u = -1.  One wave per (point, direction); no input makes the kernel read outside grey.  1 <= R <= 7, 1 <= S <= 24,
+ * 0 <= tau <= 255, 0 <= q < T, H and W < 2^15; anything else returns S2D_ERR_ARG. */
 int s2d_block_track_u8(const uint8_t *grey, int T, int H, int W, const int *points, int N, int q, int backward, int R, int S,
                        int tau, float *tracks, uint8_t *vis, hipStream_t stream);
 

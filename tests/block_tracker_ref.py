@@ -146,44 +146,45 @@ class TruthTracker(S.StubTracker):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the truth
-def call_mask(name, q, obj):
+# `scenes`: the table that holds scene `name` (tests/live_tracker_ref.py passes its own)
+def call_mask(name, q, obj, scenes=S.SCENES):
     """u8 [H,W] with {0,255}: the stage-1 mask of object `obj` in frame q"""
-    return ((S.label_map(S.SCENES[name], q) == obj + 1) * 255).astype(np.uint8)
+    return ((S.label_map(scenes[name], q) == obj + 1) * 255).astype(np.uint8)
 
 
-def call_points(name, q, obj):
-    sc = S.SCENES[name]
+def call_points(name, q, obj, scenes=S.SCENES):
+    sc = scenes[name]
     g = grid_ref(50, sc["H"], sc["W"])
-    return g[call_mask(name, q, obj)[g[:, 1], g[:, 0]] > 0]
+    return g[call_mask(name, q, obj, scenes)[g[:, 1], g[:, 0]] > 0]
 
 
-def truth(name, q, points, obj):
+def truth(name, q, points, obj, scenes=S.SCENES):
     """int [T,N,2]: every point moved by the object's step per frame"""
-    sc = S.SCENES[name]
+    sc = scenes[name]
     dy, dx = sc["objects"][obj]["step"]
     dt = np.arange(sc["T"])[:, None] - q
     return np.stack([points[None, :, 0] + dx * dt, points[None, :, 1] + dy * dt], -1)
 
 
-def _patch_labels(name, t, xy, R):
+def _patch_labels(name, t, xy, R, scenes):
     """(int [N,P,P] labels of the patch round xy in frame t, bool [N] the patch lies inside the frame)"""
-    sc = S.SCENES[name]
+    sc = scenes[name]
     H, W = sc["H"], sc["W"]
     inside = (xy[:, 0] - R >= 0) & (xy[:, 0] + R < W) & (xy[:, 1] - R >= 0) & (xy[:, 1] + R < H)
     return _patches(S.label_map(sc, t), xy[:, 0], xy[:, 1], R), inside
 
 
-def clean(name, q, points, obj, backward, R=R, S_=SEARCH):
+def clean(name, q, points, obj, backward, R=R, S_=SEARCH, scenes=S.SCENES):
     """bool [T,N]: point-frame (t, n) is continuously clean -- at every frame from q to t the (2R+1)^2 patch at the true position
     lies wholly inside the frame and shows the point's object only, and the object steps by at most S per axis"""
-    sc = S.SCENES[name]
+    sc = scenes[name]
     T = sc["T"]
-    tr = truth(name, q, points, obj)
+    tr = truth(name, q, points, obj, scenes)
     ok = np.zeros((T, len(points)), bool)
     if max(abs(s) for s in sc["objects"][obj]["step"]) > S_:
         return ok
     for t in range(T):
-        lab, inside = _patch_labels(name, t, tr[t], R)
+        lab, inside = _patch_labels(name, t, tr[t], R, scenes)
         ok[t] = inside & (lab == obj + 1).all((1, 2))
     out = np.zeros_like(ok)
     out[q:] = np.logical_and.accumulate(ok[q:], 0)
@@ -192,14 +193,14 @@ def clean(name, q, points, obj, backward, R=R, S_=SEARCH):
     return out
 
 
-def replaced(name, q, points, obj, backward, R=R):
+def replaced(name, q, points, obj, backward, R=R, scenes=S.SCENES):
     """bool [T,N]: the whole patch at the true position lies inside the frame and shows only other textures (another object's
     or the background's).  A true position whose patch leaves the frame shows nothing and is not claimed."""
-    sc = S.SCENES[name]
-    tr = truth(name, q, points, obj)
+    sc = scenes[name]
+    tr = truth(name, q, points, obj, scenes)
     out = np.zeros((sc["T"], len(points)), bool)
     for t in range(0 if backward else q, sc["T"]):
-        lab, inside = _patch_labels(name, t, tr[t], R)
+        lab, inside = _patch_labels(name, t, tr[t], R, scenes)
         out[t] = inside & (lab != obj + 1).all((1, 2))
     return out
 

@@ -143,60 +143,25 @@ def scene_grey(name):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the truth
+# block_tracker_ref's helpers on the scenes of this module
 def call_mask(name, q, obj):
-    """u8 [H,W] with {0,255}: the stage-1 mask of object `obj` in frame q"""
-    return ((S.label_map(SCENES[name], q) == obj + 1) * 255).astype(np.uint8)
+    return B.call_mask(name, q, obj, SCENES)
 
 
 def call_points(name, q, obj):
-    sc = SCENES[name]
-    g = B.grid_ref(50, sc["H"], sc["W"])
-    return g[call_mask(name, q, obj)[g[:, 1], g[:, 0]] > 0]
+    return B.call_points(name, q, obj, SCENES)
 
 
 def truth(name, q, points, obj):
-    """int [T,N,2]: every point moved by the object's step per frame"""
-    sc = SCENES[name]
-    dy, dx = sc["objects"][obj]["step"]
-    dt = np.arange(sc["T"])[:, None] - q
-    return np.stack([points[None, :, 0] + dx * dt, points[None, :, 1] + dy * dt], -1)
-
-
-def _patch_labels(name, t, xy, R):
-    sc = SCENES[name]
-    H, W = sc["H"], sc["W"]
-    inside = (xy[:, 0] - R >= 0) & (xy[:, 0] + R < W) & (xy[:, 1] - R >= 0) & (xy[:, 1] + R < H)
-    return B._patches(S.label_map(sc, t), xy[:, 0], xy[:, 1], R), inside
+    return B.truth(name, q, points, obj, SCENES)
 
 
 def clean(name, q, points, obj, backward, R=R, S_=SEARCH):
-    """bool [T,N]: point-frame (t, n) is continuously clean -- at every frame from q to t the (2R+1)^2 patch at the true position
-    lies wholly inside the frame and shows the point's object only, and the object steps by at most S per axis"""
-    sc = SCENES[name]
-    T = sc["T"]
-    tr = truth(name, q, points, obj)
-    ok = np.zeros((T, len(points)), bool)
-    if max(abs(s) for s in sc["objects"][obj]["step"]) > S_:
-        return ok
-    for t in range(T):
-        lab, inside = _patch_labels(name, t, tr[t], R)
-        ok[t] = inside & (lab == obj + 1).all((1, 2))
-    out = np.zeros_like(ok)
-    out[q:] = np.logical_and.accumulate(ok[q:], 0)
-    if backward:
-        out[:q + 1] = np.logical_and.accumulate(ok[q::-1], 0)[::-1]
-    return out
+    return B.clean(name, q, points, obj, backward, R, S_, SCENES)
 
 
 def replaced(name, q, points, obj, backward, R=R):
-    """bool [T,N]: the whole patch at the true position lies inside the frame and shows only other textures"""
-    sc = SCENES[name]
-    tr = truth(name, q, points, obj)
-    out = np.zeros((sc["T"], len(points)), bool)
-    for t in range(0 if backward else q, sc["T"]):
-        lab, inside = _patch_labels(name, t, tr[t], R)
-        out[t] = inside & (lab != obj + 1).all((1, 2))
-    return out
+    return B.replaced(name, q, points, obj, backward, R, SCENES)
 
 
 # ------------------------------------------------------------------------------------- references, computed once and shared

@@ -96,6 +96,11 @@ def test_small_frame_equals_the_reference(params):
         assert np.array_equal(got_v, want_v), (q, back)
         assert np.array_equal(got_t, want_t), (q, back)
         moved += int((want_t != pts[None].astype(np.float32)).any(-1).sum())
+        if tau == 0:
+            # among the searched frames both outcomes occur: with tau = 0 an invisible point is one whose every candidate was
+            # pruned by the cost bound, so the reduced key never left ~0
+            searched = want_v[np.arange(T) != q] if back else want_v[q + 1:]
+            assert (searched == 1).any() and (searched == 0).any(), (q, back)
     assert moved > 0 or S_ < 4                              # 5 px per frame is beyond a search radius of 1
 
 
