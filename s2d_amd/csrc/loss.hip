@@ -12,8 +12,22 @@
 // Points come from an injected coordinate buffer (parity mode: the recorded torch.rand draws) or from a
 // counter-based RNG keyed by (seed, row, index), so re-sampling in every pass is free of HBM traffic.
 // All partial sums land in fixed slots and are reduced in a fixed order (double): deterministic losses.
+//
+// THE TIE RULE.  The selected set is "the n_unc smallest |logit|"; among points whose |logit| equals the n_unc-th smallest bit for bit
+// the reference's torch.topk leaves the choice open.  Here it is defined: ascending |x|, then ascending POINT INDEX within the row's
+// oversampled points (what a stable argsort gives, and what oracle/ does).  With `take` = n_unc - #(keys below the threshold), the
+// take tied points of lowest index are kept, on every path:
+//   - rows whose samples are kept (accumulate_stream_kernel, forward and backward): a list of up to TIECAP ties ranked by index, a
+//     block scan beyond; the backward applies a per-tie ownership test per map part (injected points) or carries the ties spent by
+//     the earlier parts' index ranges (generated points, tie_before);
+//   - rows whose samples are not kept (3P or P/4 not a multiple of 4, H*W not a multiple of 32, active rows beyond XBUF_MAX_ROWS):
+//     accumulate_kernel keeps every tie when take equals their number (select_kernel<2> leaves that number in LossParams::tie) and
+//     none otherwise; accumulate_ties_kernel then adds the first `take` by index.
+// The rule depends on neither the map part a point lies in nor on how workgroups are scheduled, so two runs give the same bits.
+// tests/test_gpu_point_loss_ties.py pins it with inputs whose keys tie exactly.
 #include "common.h"
 #include "class_select.h"
+#include <climits>
 
 namespace {
 
@@ -255,7 +269,7 @@ struct LossParams {
     unsigned int *hist;       // [rows][2048]
     unsigned int *prefix;     // [rows]  key prefix found so far
     int *krem;                // [rows]  how many still to take inside the prefix
-    unsigned int *tie;        // [rows]
+    unsigned int *tie;        // [rows]  how many points sit AT the threshold key (select_kernel<2>); krem of them are taken
     float *part;              // [rows][chunks][4]
     int chunks;
     float *xbuf;              // [xcap][n_over + n_rand]: sampled logits of the first xcap active rows (sampled ONCE)
@@ -829,6 +843,7 @@ __global__ __launch_bounds__(256) void select_kernel(LossParams p)
             const unsigned int pre = LEVEL == 0 ? 0u : p.prefix[rowid];
             p.prefix[rowid] = LEVEL == 0 ? (bin << 20) : LEVEL == 1 ? (pre | (bin << 10)) : (pre | bin);
             p.krem[rowid] = k - (int)before;
+            if (LEVEL == 2) p.tie[rowid] = loc[j];                 // a level-2 bin is one key: the number of points AT the threshold
         }
         before += loc[j];
     }
@@ -868,6 +883,10 @@ __global__ __launch_bounds__(LTHREADS) void accumulate_kernel(LossParams p)
         const uint8_t *pl = p.tgt + (((long)b * p.Nmax + n) * p.T + t) * p.H * p.W;
         const unsigned int thr = p.prefix[rowid];
         const unsigned int take = (unsigned int)p.krem[rowid];
+        // points AT the threshold (select_kernel<2> counted them: take <= p.tie[rowid]): all of them are kept -- the usual row, whose only
+        // such point is the threshold element itself -- or the `take` with the smallest point index, which no part of the row can tell on
+        // its own: those are left out here and added by accumulate_ties_kernel
+        const bool all_ties = take > 0u && take == p.tie[rowid];
         const int ylo = part == 0 ? -1 : r0, yhi = r0 + g.rows_per_part;
         float bce = 0.f, sgt = 0.f, sg = 0.f, ts = 0.f;
 #pragma unroll 1
@@ -909,8 +928,7 @@ __global__ __launch_bounds__(LTHREADS) void accumulate_kernel(LossParams p)
                     bool sel = own[j];
                     if (over && sel) {
                         const unsigned int key = __float_as_uint(fabsf(xv[j]));
-                        sel = key < thr;
-                        if (key == thr) sel = atomicAdd(&p.tie[rowid], 1u) < take;
+                        sel = key < thr || (all_ties && key == thr);
                     }
                     if (sel) acc_point(xv[j], sample_plane(pl, p.H, p.W, uu[j], vv[j]), bce, sgt, sg, ts);
                 }
@@ -926,6 +944,105 @@ __global__ __launch_bounds__(LTHREADS) void accumulate_kernel(LossParams p)
 #pragma unroll
             for (int w = 0; w < LTHREADS / 64; ++w) tot += red[w][j];
             p.part[(rowid * p.chunks + part) * 4 + j] = tot;
+        }
+    }
+}
+
+// bilinear sample of a row's [hm,wm] map in global memory at (x, y) with the tap corner (x0, y0) given: the products and the order of
+// additions of sample_part / sample_part_padded (a tap outside the map contributes a zero), so |result| has the bits the select saw
+__device__ __forceinline__ float sample_map_at(const float *__restrict__ map, int hm, int wm, float x, float y, int x0, int y0)
+{
+    const int x1 = x0 + 1, y1 = y0 + 1;
+    const float fx = x - x0, fy = y - y0;
+    const bool xa_in = x0 >= 0 && x0 < wm, xb_in = x1 >= 0 && x1 < wm, ya_in = y0 >= 0 && y0 < hm, yb_in = y1 >= 0 && y1 < hm;
+    const int xa = min(max(x0, 0), wm - 1), xb = min(max(x1, 0), wm - 1);
+    const int ya = min(max(y0, 0), hm - 1) * wm, yb = min(max(y1, 0), hm - 1) * wm;
+    float acc = (xa_in && ya_in ? map[ya + xa] : 0.f) * ((1.f - fx) * (1.f - fy));
+    acc += (xb_in && ya_in ? map[ya + xb] : 0.f) * (fx * (1.f - fy));
+    acc += (xa_in && yb_in ? map[yb + xa] : 0.f) * ((1.f - fx) * fy);
+    acc += (xb_in && yb_in ? map[yb + xb] : 0.f) * (fx * fy);
+    return acc;
+}
+
+// The tie rule for the rows accumulate_kernel handles (samples not kept): of the points whose |logit| EQUALS the threshold, the `take`
+// with the smallest point index over the whole row are kept -- the streamed kernel's rule, whatever the map part a point lies in and
+// however the workgroups are scheduled.  One workgroup per such row that has more ties than it takes (a row of a smooth map has one,
+// the threshold element, and is skipped): the oversampled points are walked in index order, 512 at a time, re-sampled from the row's
+// map in global memory, ranked among the ties by a block scan (as accumulate_stream_kernel's scan path), and the first `take` are
+// evaluated; the walk ends with the take-th tie.  The sums go on top of the row's part-0 slot: this kernel runs after
+// accumulate_kernel, one thread per slot entry, so the order of the additions is fixed.
+__global__ __launch_bounds__(LTHREADS) void accumulate_ties_kernel(LossParams p)
+{
+    __shared__ float red[LTHREADS / 64][4];
+    __shared__ unsigned int wtie[LTHREADS / 64], tie_base;
+    __shared__ float s_v0[PB_STRIDE], s_dv[PB_STRIDE];
+    const int nrows = p.lcount[p.NL];
+    if (p.xcap + (int)blockIdx.x >= nrows) return;                   // the launch is decided on the padded row count: usually no row is left
+    const PartGeom g = part_geom(p.hm, p.wm);
+    if ((int)threadIdx.x < g.nparts) { const VRange vr = part_vrange(threadIdx.x, g.nparts, g.rows_per_part, p.hm); s_v0[threadIdx.x] = vr.v0; s_dv[threadIdx.x] = vr.dv; }
+    const int rows_l = p.B * p.maxm * p.T;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int li = p.xcap + (int)blockIdx.x; li < nrows; li += gridDim.x) {
+        const long rowid = p.list[li];
+        const unsigned int thr = p.prefix[rowid];
+        const unsigned int take = (unsigned int)p.krem[rowid];
+        if (take == 0u || take >= p.tie[rowid]) continue;            // uniform over the workgroup: accumulate_kernel kept every tie
+        __syncthreads();
+        if (threadIdx.x == 0) tie_base = 0u;
+        __syncthreads();
+        const int r = (int)(rowid % rows_l);
+        const int t = r % p.T, s = (r / p.T) % p.maxm, b = r / (p.T * p.maxm);
+        const int prob = (int)(rowid / rows_l) * p.B + b;
+        const int n = p.idx_t[(long)prob * p.maxm + s];
+        const uint8_t *pl = p.tgt + (((long)b * p.Nmax + n) * p.T + t) * p.H * p.W;
+        const float *map = p.mq + rowid * p.hm * p.wm;
+        const float *cr = coord_rows(p, rowid, true);
+        const uint32_t key0 = rand_key(p.seed, key_row(p, rowid) * 2);
+        const int *pb = p.pbound + rowid * PB_STRIDE;
+        float bce = 0.f, sgt = 0.f, sg = 0.f, ts = 0.f;
+        for (int i0 = 0; i0 < p.n_over; i0 += LTHREADS) {
+            const int i = i0 + (int)threadIdx.x;
+            float u = 0.f, v = 0.f, xv = 0.f;
+            bool istie = false;
+            if (i < p.n_over) {
+                int ylo = INT_MIN, y0max = INT_MAX;                 // generator mode: floor(y) is clamped into the point's own part, as the select did
+                if (cr) { u = cr[2 * i]; v = cr[2 * i + 1]; }
+                else {
+                    int j = 0;
+                    while (j + 1 < g.nparts && i >= pb[j + 1]) ++j;
+                    over_point_rng(key0, i, pb, s_v0, s_dv, g.nparts, u, v);
+                    ylo = j == 0 ? -1 : j * g.rows_per_part;
+                    y0max = min((j + 1) * g.rows_per_part, p.hm) - 1;
+                }
+                const float y = ((2.f * v - 1.f + 1.f) * p.hm - 1.f) * 0.5f;
+                const float x = ((2.f * u - 1.f + 1.f) * p.wm - 1.f) * 0.5f;
+                xv = sample_map_at(map, p.hm, p.wm, x, y, (int)floorf(x), min(max((int)floorf(y), ylo), y0max));
+                istie = __float_as_uint(fabsf(xv)) == thr;
+            }
+            const unsigned long long bal = __ballot(istie);
+            if (lane == 0) wtie[wv] = (unsigned int)__popcll(bal);
+            __syncthreads();
+            unsigned int rank = tie_base + (unsigned int)__popcll(bal & ((1ull << lane) - 1ull));
+            for (int w = 0; w < wv; ++w) rank += wtie[w];
+            if (istie && rank < take) acc_point(xv, sample_plane(pl, p.H, p.W, u, v), bce, sgt, sg, ts);
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                unsigned int tot = 0u;
+                for (int w = 0; w < LTHREADS / 64; ++w) tot += wtie[w];
+                tie_base += tot;
+            }
+            __syncthreads();
+            if (tie_base >= take) break;                             // uniform: read after the barrier, written again only after the next two
+        }
+        bce = wave_sum(bce); sgt = wave_sum(sgt); sg = wave_sum(sg); ts = wave_sum(ts);
+        if (lane == 0) { red[wv][0] = bce; red[wv][1] = sgt; red[wv][2] = sg; red[wv][3] = ts; }
+        __syncthreads();
+        if (threadIdx.x < 4) {
+            const int j = threadIdx.x;
+            float tot = 0.f;
+#pragma unroll
+            for (int w = 0; w < LTHREADS / 64; ++w) tot += red[w][j];
+            p.part[(rowid * p.chunks + 0) * 4 + j] += tot;
         }
     }
 }
@@ -1677,7 +1794,10 @@ int s2d_point_loss_f32(const float *mask_logits, const uint8_t *tgt, const int *
         hipLaunchKernelGGL(accumulate_stream_kernel<false>, dim3(ACC_BLOCKS), dim3(LTHREADS), (size_t)((long)H * W / 8), stream, p, LossBwdArgs{nullptr, 0.f, 0.f, nullptr});
     else if (p.xcap > 0)
         hipLaunchKernelGGL((accumulate_stream_kernel<false, true>), dim3(ACC_BLOCKS), dim3(LTHREADS), 16, stream, p, LossBwdArgs{nullptr, 0.f, 0.f, nullptr});
-    if (rows > p.xcap) hipLaunchKernelGGL(accumulate_kernel, g, dim3(LTHREADS), lds_map, stream, p);
+    if (rows > p.xcap) {
+        hipLaunchKernelGGL(accumulate_kernel, g, dim3(LTHREADS), lds_map, stream, p);
+        hipLaunchKernelGGL(accumulate_ties_kernel, g, dim3(LTHREADS), 0, stream, p);
+    }
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(NL), dim3(64), 0, stream, p, losses);
     S2D_CHECK_LAUNCH();
     return S2D_OK;

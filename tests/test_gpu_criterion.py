@@ -299,7 +299,8 @@ def test_matcher_three_32_row_tiles_plus_one_16_row_tile(monkeypatch):
 @pytest.mark.parametrize("P,H,W", [(250, 64, 96), (256, 64, 96), (1000, 32, 128)])
 def test_point_loss_vs_oracle_both_paths(oracle, P, H, W):
     """point loss vs the CPU restatement where the sampled logits cannot be kept (3P or P/4 not a multiple of 4: the
-    recompute kernels) and where they can (the streamed kernels), same call"""
+    recompute kernels) and where they can (the streamed kernels): each parametrisation takes ONE of the two paths; a single call
+    that takes both (more than 4096 active rows) is tests/test_gpu_point_loss_ties.py::test_more_than_4096_rows_in_one_call"""
     from s2d_amd import ops
     B, Q, T, h, w = 2, 16, 2, H // 4, W // 4
     ns = [3, 2]
