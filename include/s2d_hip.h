@@ -457,7 +457,8 @@ int s2d_pack_mask_bits_u8(const uint8_t *masks, int K, long n, uint32_t *bits, h
 
 /* inter[i][j] = sum(mask_i & mask_j) for all pairs of K bit-packed masks (diagonal = areas; sum(mask_i | mask_j) =
  * inter[i][i] + inter[j][j] - inter[i][j]): everything the greedy mask-NMS of :552-583 reads, in one launch instead
- * of two full-tensor reductions and a host sync per pair.  inter [K][K] (zeroed here). */
+ * of two full-tensor reductions and a host sync per pair.  inter [K][K] (zeroed here).  This call, s2d_mask_plane_areas_u32,
+ * s2d_mask_cross_counts_u64 and s2d_mask_frame_cross_counts_i32 are one set of kernels (csrc/mask_counts.hip). */
 int s2d_mask_pair_counts_u64(const uint32_t *bits, int K, long words, unsigned long long *inter, hipStream_t stream);
 
 /* ---- COCO run-length encoding of masks (wire format after inference_video / of the keymask annotations) ------- */
@@ -579,7 +580,7 @@ int s2d_disk_dilate_bits_u32(const uint32_t *bits, int F, int H, int W, int R, u
 
 /* out [P][G][T] int32 = popcount(a[p][t] & b[g][t]) per frame, for a [P][T][words_per_frame] and b [G][T][words_per_frame]; zeroed
  * by the call.  T < 65536, words_per_frame < 2^26 (a plane of fewer than 2^31 pixels: every count fits).  The per-frame
- * companion of s2d_mask_cross_counts_u64, which sums whole tracks. */
+ * companion of s2d_mask_cross_counts_u64, which sums whole tracks (the same kernel, csrc/mask_counts.hip). */
 int s2d_mask_frame_cross_counts_i32(const uint32_t *a, int P, const uint32_t *b, int G, int T, long words_per_frame, int *out,
                                     hipStream_t stream);
 

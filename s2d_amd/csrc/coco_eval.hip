@@ -3,18 +3,19 @@
 // holds.  The ragged layout (flat buffers + per-image offset tables) is documented in include/s2d_hip.h.
 //
 //   ragged_mask_iou_kernel  one workgroup per 8 x 8 tile of (detection, ground truth) pairs of one image (the host lists the
-//                           tiles): every word of the 16 planes is loaded once per tile, the tile's 64 intersection counts and
-//                           16 plane areas are exact integers, and the IoU is one float64 division of them in the epilogue.  A
-//                           tile is owned by one workgroup: no atomics, no zero fill, bitwise deterministic.
+//                           tiles): every word of the 16 planes is loaded once per tile (PopcTile of bitplane.h, which also
+//                           states the plane layout), the tile's 64 intersection counts and 16 plane areas are exact integers,
+//                           and the IoU is one float64 division of them in the epilogue.  A tile is owned by one workgroup: no
+//                           atomics, no zero fill, bitwise deterministic.
 //   ragged_box_iou_kernel   one thread per pair, maskApi.c bbIou's operation order in float64 (the build has -ffp-contract=off).
 //   coco_match_kernel       COCOeval.evaluateImg's greedy loop.  One workgroup per group (an image, or an image and a category):
 //                           lane (a, t) runs area range a at threshold t -- the thresholds and the ranges are independent, the
 //                           detection loop is sequential by definition.
-#include "common.h"
+#include "bitplane.h"
 
 namespace {
 
-constexpr int CT = 8;                       // pair tile edge, as cross_count_kernel (ytvis_eval.hip)
+constexpr int CT = 8;                       // pair tile edge
 constexpr int IMG_COLS = 9;                 // columns of an image-table row (s2d_hip.h)
 constexpr int GRP_COLS = 8;                 // columns of a group-table row
 
@@ -32,13 +33,11 @@ __global__ __launch_bounds__(256) void ragged_mask_iou_kernel(const uint32_t *__
     const long dt0 = im[6], gt0 = im[7], pair0 = im[8];
     const uint32_t tail = (hw & 31) ? ((1u << (hw & 31)) - 1u) : 0xffffffffu;       // bits past H*W in the last word do not count
 
-    unsigned int acc[CT][CT], pa[CT], pb[CT];
+    PopcTile<CT> tile;
+    tile.zero();
+    unsigned int pa[CT], pb[CT];
 #pragma unroll
-    for (int p = 0; p < CT; ++p) {
-        pa[p] = pb[p] = 0u;
-#pragma unroll
-        for (int q = 0; q < CT; ++q) acc[p][q] = 0u;
-    }
+    for (int p = 0; p < CT; ++p) pa[p] = pb[p] = 0u;
     for (long w = threadIdx.x; w < wpp; w += 256) {
         const uint32_t keep = w == wpp - 1 ? tail : 0xffffffffu;
         unsigned int va[CT], vb[CT];
@@ -50,21 +49,11 @@ __global__ __launch_bounds__(256) void ragged_mask_iou_kernel(const uint32_t *__
             pa[p] += __popc(va[p]);
             pb[p] += __popc(vb[p]);
         }
-#pragma unroll
-        for (int p = 0; p < CT; ++p)
-#pragma unroll
-            for (int q = 0; q < CT; ++q) acc[p][q] += __popc(va[p] & vb[q]);
+        tile.add(va, vb);
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
-    for (int p = 0; p < CT; ++p) {
-#pragma unroll
-        for (int q = 0; q < CT; ++q) {
-            unsigned int v = acc[p][q];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            if (lane == 0) red[wv][p * CT + q] = v;
-        }
+    for (int p = 0; p < CT; ++p) {                                            // the areas ride in the columns behind the tile's
         unsigned int a = pa[p], b = pb[p];
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
@@ -76,14 +65,13 @@ __global__ __launch_bounds__(256) void ragged_mask_iou_kernel(const uint32_t *__
             red[wv][CT * CT + CT + p] = b;
         }
     }
-    __syncthreads();
+    const long long n = (long long)tile.reduce(red);                          // ends in the barrier that covers the areas too
     const int x = threadIdx.x;
     if (x < CT * CT) {
         const int p = x / CT, q = x % CT;
         const int i = ti * CT + p, j = tj * CT + q;
         if (i < D && j < G) {
             const int ap = CT * CT + p, aq = CT * CT + CT + q;
-            const long long n = (long long)red[0][x] + red[1][x] + red[2][x] + red[3][x];
             const long long ad = (long long)red[0][ap] + red[1][ap] + red[2][ap] + red[3][ap];
             const long long ag = (long long)red[0][aq] + red[1][aq] + red[2][aq] + red[3][aq];
             const long long u = crowd[gt0 + j] ? ad : ad + ag - n;

@@ -12,8 +12,8 @@
 // Here: one selection kernel; the K selected queries' logits are gathered from the pixel-major maps into small planes;
 // one kernel evaluates both bilinear stages per output pixel (16 low-resolution taps, the same fp32 expression tree as
 // two consecutive F.interpolate calls) and writes the boolean mask once, as bytes (the tensor the caller gets) and as
-// bit words; a tiled popcount kernel turns the bit words into the K x K intersection counts, from which the host runs
-// the greedy loop without touching the masks again.
+// bit words; the tiled popcount kernel of mask_counts.hip (s2d_mask_pair_counts_u64) turns the bit words into the K x K
+// intersection counts, from which the host runs the greedy loop without touching the masks again.
 #include "common.h"
 #include "class_select.h"
 
@@ -225,62 +225,8 @@ __global__ __launch_bounds__(256) void infer_resize_kernel(ResizeParams p)
     }
 }
 
-// inter[i][j] += sum over a chunk of words of popcount(bits[i] & bits[j]) for an 8 x 8 tile of mask pairs (tile row <=
-// tile column; the diagonal holds the areas).  Integer atomics: the result does not depend on the order.
-constexpr int PT = 8;
-__global__ __launch_bounds__(256) void pair_count_kernel(const uint32_t *__restrict__ bits, int K, long words, int ntile,
-                                                         unsigned long long *__restrict__ inter)
-{
-    __shared__ unsigned int red[4][PT * PT];
-    // blockIdx.y enumerates the tile pairs (ti <= tj)
-    int ti = 0, rem = blockIdx.y;
-    while (rem >= ntile - ti) { rem -= ntile - ti; ++ti; }
-    const int tj = ti + rem;
-    unsigned int acc[PT][PT];
-#pragma unroll
-    for (int a = 0; a < PT; ++a)
-#pragma unroll
-        for (int b = 0; b < PT; ++b) acc[a][b] = 0u;
-    const long per = (words + gridDim.x - 1) / gridDim.x;
-    const long w0 = (long)blockIdx.x * per, w1 = w0 + per < words ? w0 + per : words;
-    for (long w = w0 + threadIdx.x; w < w1; w += 256) {
-        unsigned int va[PT], vb[PT];
-#pragma unroll
-        for (int a = 0; a < PT; ++a) {
-            const int i = ti * PT + a, j = tj * PT + a;
-            va[a] = i < K ? bits[(long)i * words + w] : 0u;
-            vb[a] = j < K ? bits[(long)j * words + w] : 0u;
-        }
-#pragma unroll
-        for (int a = 0; a < PT; ++a)
-#pragma unroll
-            for (int b = 0; b < PT; ++b) acc[a][b] += __popc(va[a] & vb[b]);
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int a = 0; a < PT; ++a)
-#pragma unroll
-        for (int b = 0; b < PT; ++b) {
-            unsigned int v = acc[a][b];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            if (lane == 0) red[wv][a * PT + b] = v;
-        }
-    __syncthreads();
-    if (threadIdx.x < PT * PT) {
-        const int a = threadIdx.x / PT, b = threadIdx.x % PT;
-        const int i = ti * PT + a, j = tj * PT + b;
-        const unsigned long long v = (unsigned long long)red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        if (i < K && j < K && v) {
-            atomicAdd(&inter[(long)i * K + j], v);
-            if (ti != tj) atomicAdd(&inter[(long)j * K + i], v);
-        }
-    }
-}
-
-
 // u8 mask planes [K][n] (0 / non-0) -> bit words [K][ceil(n / 32)] (flat index i -> word i / 32, bit i % 32; tail bits zero):
-// the input format of pair_count_kernel, for masks that exist as byte planes (the KD pseudo targets, DISTILLATION_NMS)
+// the input format of s2d_mask_pair_counts_u64 (mask_counts.hip), for masks that exist as byte planes (the KD pseudo targets, DISTILLATION_NMS)
 __global__ __launch_bounds__(256) void pack_bits_kernel(const uint8_t *__restrict__ masks, long n, long words, uint32_t *__restrict__ bits)
 {
     const int k = blockIdx.y;
@@ -542,23 +488,6 @@ int s2d_pack_mask_bits_u8(const uint8_t *masks, int K, long n, uint32_t *bits, h
     const long words = (n + 31) / 32;
     if ((words * 32 + 255) / 256 >= (1L << 31)) return S2D_ERR_ARG;
     hipLaunchKernelGGL(pack_bits_kernel, dim3(cdiv(words * 32, 256), K), dim3(256), 0, stream, masks, n, words, bits);
-    S2D_CHECK_LAUNCH();
-    return S2D_OK;
-}
-
-int s2d_mask_pair_counts_u64(const uint32_t *bits, int K, long words, unsigned long long *inter, hipStream_t stream)
-{
-    if (K < 0 || words < 0) return S2D_ERR_ARG;
-    if (K == 0) return S2D_OK;
-    if (s2d_zero_async(inter, sizeof(unsigned long long) * (size_t)K * K, stream) != S2D_OK) return S2D_ERR_LAUNCH;
-    if (words == 0) return S2D_OK;
-    const int ntile = (K + PT - 1) / PT;
-    const int npairs = ntile * (ntile + 1) / 2;
-    int chunks = cdiv(words, 256 * 16);                 // >= 16 words per thread
-    const int want = cdiv(2048, npairs);                // enough workgroups to fill 256 CUs
-    if (chunks > want) chunks = want;
-    if (chunks < 1) chunks = 1;
-    hipLaunchKernelGGL(pair_count_kernel, dim3(chunks, npairs), dim3(256), 0, stream, bits, K, words, ntile, inter);
     S2D_CHECK_LAUNCH();
     return S2D_OK;
 }

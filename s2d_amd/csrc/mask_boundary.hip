@@ -3,21 +3,18 @@
 // with everything outside the image counting as 0.  d such erosions are one erosion by a (2d+1) x (2d+1) square with a zero
 // border, and that square is separable:  E[y][x] = AND_{|dy| <= d} Eh[y + dy][x],  Eh[y][x] = AND_{|dx| <= d} M[y][x + dx].
 //
-// Planes are flat (pixel i -> word i/32, bit i%32: rows are not word-aligned unless W % 32 == 0); the kernel works on
-// ROW-ALIGNED words (row y, word k = pixels 32k .. 32k+31 of that row, pixels at and beyond W zero).
+// Planes are flat and the kernel works on row-aligned words: the layout and the helpers shared with the disk dilation of
+// davis_eval.hip are in bitplane.h.
 //
 //   erode_tile_kernel   one workgroup per tile of TR rows x TW row-aligned words of one plane, r <= 64:
 //     1. horizontal, in registers: for every word of the tile and of its r halo rows above and below, the 192 row bits
 //        around it (pixels 32k-64 .. 32k+127, seven flat words funnelled into three u64, pixels outside the row masked to
 //        0: that is the zero border, and it drops whatever sits in a plane's padding bits) are ANDed over a window of
-//        n = 2r+1 bits by doubling: A_1 = V, A_2a = A_a & (A_a >> a) up to the largest power of two p <= n, then
-//        A_p & (A_p >> (n - p)) -- AND is idempotent, so two overlapping windows of p make one of n.  The word goes to LDS;
-//        halo rows outside the image are 0.
+//        n = 2r+1 bits by doubling (window192).  The word goes to LDS; halo rows outside the image are 0.
 //     2. vertical, in LDS: the same doubling over rows as plain word ANDs, ping-pong between two buffers (flat indices,
 //        adjacent lanes on adjacent words: no bank conflicts), one barrier per step.
-//     3. M & ~E (or E itself for an intermediate pass), written back to the flat layout: plain stores when rows are
-//        word-aligned, otherwise each row-aligned word is ORed into the one or two flat words it covers (out zeroed first;
-//        only pixel bits are ever set, so a plane's padding bits stay 0).  OR commutes: the result is bitwise deterministic.
+//     3. M & ~E (or E itself for an intermediate pass), written back to the flat layout (store_row_word; out zeroed first
+//        when rows are not word-aligned).
 //
 // d > 64 (frames beyond 4K at the default ratio) chains erosions: squares add up, erode(r1 + r2) = erode(r2) o erode(r1),
 // also with the zero border (an eroded plane is zero outside the image like its input).  The intermediates alternate between
@@ -27,7 +24,7 @@
 //   erode_ragged_kernel  the same tile body for a chunk of images of different sizes in ONE launch (the COCO image evaluator,
 //     s2d_amd/coco_eval.py): every image has its own H, W, d and tile shape, listed in a plan table that the host derives and
 //     re-checks before the launch; one pass only (clamped d <= 64), the last one: out = M & ~E.
-#include "common.h"
+#include "bitplane.h"
 
 #include <vector>
 
@@ -37,20 +34,6 @@ constexpr int BD_T = 256;
 constexpr int BD_RMAX = 64;         // one pass: the 192-bit window holds 64 pixels either side of a word
 constexpr int BD_CAP = 8192;        // words per LDS buffer (two buffers: 64 KiB, two workgroups per CU)
 constexpr int BD_TW = 32;           // row-aligned words per tile row at most
-
-struct u192 { unsigned long long a, b, c; };   // bit i of the window: a = 0..63, b = 64..127, c = 128..191
-
-// bits i + s -> i, zeros in at the top; 1 <= s <= 64
-__device__ __forceinline__ u192 shr192(u192 v, int s)
-{
-    u192 o;
-    if (s == 64) { o.a = v.b; o.b = v.c; o.c = 0ull; return o; }
-    o.a = (v.a >> s) | (v.b << (64 - s));
-    o.b = (v.b >> s) | (v.c << (64 - s));
-    o.c = v.c >> s;
-    return o;
-}
-__device__ __forceinline__ u192 and192(u192 x, u192 y) { u192 o = {x.a & y.a, x.b & y.b, x.c & y.c}; return o; }
 
 // bits [lo, hi) of a 64-bit chunk whose first bit is window bit `base`
 __device__ __forceinline__ unsigned long long chunk_mask(int lo, int hi, int base)
@@ -85,19 +68,6 @@ __device__ __forceinline__ u192 row_window(const uint32_t *__restrict__ pl, long
     return w;
 }
 
-// pixels 32k .. 32k+31 of row y, pixels at and beyond W zero
-__device__ __forceinline__ unsigned int row_word(const uint32_t *__restrict__ pl, long wpf, int y, int W, int k)
-{
-    const long P = (long)y * W + 32 * k;
-    const long wb = P >> 5;
-    const int o = (int)(P & 31);
-    const unsigned int g0 = pl[wb];
-    const unsigned int g1 = wb + 1 < wpf ? pl[wb + 1] : 0u;
-    const unsigned int v = (unsigned int)(((((unsigned long long)g1) << 32) | g0) >> o);
-    const int n = W - 32 * k;
-    return n >= 32 ? v : (v & ((1u << n) - 1u));            // 1 <= n: the word starts inside the row
-}
-
 // One tile (row tile ty, word tile tx) of ONE plane: pl the plane to erode by r, ml the plane M for the last pass (op = M & ~E)
 // or null (op = E), op the output plane; lds: 2 * TW * (TR + 2r) words.  The body both kernels below share.
 __device__ __forceinline__ void erode_tile(const uint32_t *__restrict__ pl, const uint32_t *__restrict__ ml, uint32_t *__restrict__ op,
@@ -106,21 +76,13 @@ __device__ __forceinline__ void erode_tile(const uint32_t *__restrict__ pl, cons
 {
     const int y0 = ty * TR, k0 = tx * TW;
     const int LR = TR + 2 * r, N = TW * LR;
-    const int n = 2 * r + 1;
-    int p = 2;
-    while (2 * p <= n) p *= 2;                              // largest power of two <= n (n >= 3)
+    const int n = 2 * r + 1, p = pow2_floor(n);
     unsigned int *cur = lds, *nxt = lds + N;
 
     for (int i = threadIdx.x; i < N; i += BD_T) {
         const int ry = i / TW, k = k0 + (i - ry * TW), y = y0 - r + ry;
         unsigned int e = 0u;
-        if (y >= 0 && y < H && k < S) {
-            u192 A = row_window(pl, wpf, y, W, k);
-            for (int a = 1; a < p; a <<= 1) A = and192(A, shr192(A, a));
-            A = and192(A, shr192(A, n - p));                // window bit q = AND of pixels q .. q + 2r of the window
-            const int pos = 64 - r;                         // pixel 32k + j is the centre of the window that starts at 64 + j - r
-            e = pos == 0 ? (unsigned int)A.a : (unsigned int)((A.a >> pos) | (A.b << (64 - pos)));
-        }
+        if (y >= 0 && y < H && k < S) e = centre_word(window192<BitAnd>(row_window(pl, wpf, y, W, k), n), r);
         cur[i] = e;
     }
     __syncthreads();
@@ -130,21 +92,16 @@ __device__ __forceinline__ void erode_tile(const uint32_t *__restrict__ pl, cons
         __syncthreads();
         unsigned int *s = cur; cur = nxt; nxt = s;
     }
-    const int sh = (n - p) * TW;
+    const int sh = (n - p) * TW;                            // n is odd and >= 3: n > p
     for (int i = threadIdx.x; i < TR * TW; i += BD_T) {      // output row y0 + ry: window rows ry .. ry + 2r of the tile
         const int ry = i / TW, k = k0 + (i - ry * TW), y = y0 + ry;
         if (y >= H || k >= S) continue;
         unsigned int v = cur[i] & cur[i + sh];              // i + sh <= (TR - 1 + 2r) * TW + TW - 1 < N
+        // y < H and k < S: the word starts inside the plane.  Said aloud, row_word's first load needs no test of its own, and with
+        // that load in flight the second one does not wait for it (2.5 % of the kernel at 720p)
+        __builtin_assume(((long)y * W + 32 * k) >> 5 < wpf);
         if (ml) v = row_word(ml, wpf, y, W, k) & ~v;
-        const long P = (long)y * W + 32 * k;
-        if (aligned) {
-            op[P >> 5] = v;
-        } else if (v) {
-            const int o = (int)(P & 31);
-            atomicOr(&op[P >> 5], v << o);                  // set bits are pixels of the plane: the words exist
-            const unsigned int hi = o ? v >> (32 - o) : 0u;
-            if (hi) atomicOr(&op[(P >> 5) + 1], hi);
-        }
+        store_row_word(op, y, W, k, v, aligned);
     }
 }
 
@@ -196,28 +153,16 @@ __global__ __launch_bounds__(BD_T) void erode_ragged_kernel(const uint32_t *__re
     erode_tile(bits + at, bits + at, out + at, H, W, r, wpp, S, TW, TR, ty, tx, (W & 31) == 0, lds);
 }
 
-struct BdPlan { int d, TW, TR, ntx, nty, S; long wpf, nb; };
+struct BdPlan : TilePlan { int d; };
 
-// d clamped to where E is empty anyway; the tile: at most BD_TW words wide (rows of more words are cut evenly), as many
-// rows as one LDS buffer holds beside the 2r halo rows (>= 128), cut evenly over H
+// d clamped to where E is empty anyway; as many rows as one LDS buffer holds beside the 2r halo rows of the widest pass (>= 128)
 bool bd_plan(int F, int H, int W, int d, BdPlan *pp)
 {
-    if (F < 0 || H < 1 || W < 1 || d < 1 || (long)H * W >= (1L << 31)) return false;
-    BdPlan q;
-    const int m = H < W ? H : W;
-    q.d = d < (m + 1) / 2 ? d : (m + 1) / 2;
-    q.wpf = ((long)H * W + 31) / 32;
-    q.S = (W + 31) / 32;
-    q.ntx = cdiv(q.S, BD_TW);
-    q.TW = cdiv(q.S, q.ntx);
-    const int r = q.d < BD_RMAX ? q.d : BD_RMAX;             // the widest pass
-    const int tr_max = BD_CAP / q.TW - 2 * r;
-    q.nty = cdiv(H, tr_max);
-    q.TR = cdiv(H, q.nty);
-    q.nb = (long)q.ntx * q.nty;
-    if ((long)F * q.nb >= (1L << 31)) return false;
-    *pp = q;
-    return true;
+    if (d < 1) return false;
+    const int m = H < W ? H : W;                            // an empty image is refused below, before d is used
+    pp->d = d < (m + 1) / 2 ? d : (m + 1) / 2;
+    const int r = pp->d < BD_RMAX ? pp->d : BD_RMAX;
+    return tile_plan(F, H, W, BD_TW, [r](int TW) { return BD_CAP / TW - 2 * r; }, pp);
 }
 
 // spec [N][5] = {word0, F, H, W, d} -> plan rows, total workgroups, launch LDS bytes; false (nothing written) for a table the

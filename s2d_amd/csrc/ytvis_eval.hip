@@ -1,17 +1,15 @@
 // Per-pixel work of the YTVIS video-instance evaluator (s2d_amd/ytvis_eval.py; the reference's YTVOSeval.computeIoU,
 // mask2former_video/data_video/datasets/ytvis_api/ytvoseval.py:176-222, and YTVOS.loadRes areas, ytvos.py:239-252).
 // A pair's video IoU is sum_t |d_t & g_t| / sum_t |d_t | g_t| with absent frames counting as empty planes, so it is exact
-// from three integer quantities: the cross intersection counts of the two tracks and each track's area sum.
+// from three integer quantities: the cross intersection counts of the two tracks and each track's area sum (the popcount kernels
+// of mask_counts.hip: s2d_mask_cross_counts_u64, s2d_mask_plane_areas_u32).  This file makes the planes they count.
 //
 //   rle_parse_kernel      pycocotools rleFrString (third party, restated): one wave per string, writing the running END
 //                         of every run (the prefix the decoder searches) instead of the run lengths;
-//   rle_decode_bits_kernel run ends -> one word-aligned bit plane per frame, row-major (flat pixel i -> word i/32, bit
-//                         i%32: the layout s2d_pack_mask_bits_u8 writes).  Runs are column-major, so a wave owns 64
-//                         adjacent columns and walks down the rows: every lane advances its own run cursor (found once by
+//   rle_decode_bits_kernel run ends -> one flat bit plane per frame (the layout of bitplane.h).  Runs are column-major, so a
+//                         wave owns 64 adjacent columns and walks down the rows: every lane advances its own run cursor (found once by
 //                         a binary search at the top of its column) and the wave's ballot is one row segment of the plane;
-//   plane_popcount_kernel per-plane areas (mask_util.area);
-//   cross_count_kernel    inter[d][g] = sum popcount(A_d & B_g) over a video's words, an 8 x 8 tile of track pairs per
-//                         workgroup (each word loaded once per tile), the D x G block of pair_count_kernel (infer.hip).
+//   plane_bbox_kernel     per-plane tight boxes (mask_util.toBbox).
 #include "common.h"
 
 namespace {
@@ -143,19 +141,6 @@ __global__ __launch_bounds__(DEC_T) void rle_decode_bits_kernel(const int *__res
     }
 }
 
-__global__ __launch_bounds__(256) void plane_popcount_kernel(const uint32_t *__restrict__ bits, long wpf, unsigned int *__restrict__ area)
-{
-    __shared__ unsigned int red[4];
-    const uint32_t *pl = bits + (long)blockIdx.x * wpf;
-    unsigned int s = 0;
-    for (long w = threadIdx.x; w < wpf; w += 256) s += __popc(pl[w]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) area[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
 // bbox[f] = [x, y, w, h] of plane f: pycocotools rleToBbox (third party, restated; what mask_util.toBbox returns for the pseudo
 // annotations of keymask_ident/convert_results_to_annotations.py:72).  rleToBbox takes the extremes of the first and last pixel
 // of every run of ones (column-major), and sets the row range to [0, H-1] when a run starts in one column and ends in a later one.
@@ -206,51 +191,6 @@ __global__ __launch_bounds__(256) void plane_bbox_kernel(const uint32_t *__restr
     }
 }
 
-constexpr int CT = 8;
-__global__ __launch_bounds__(256) void cross_count_kernel(const uint32_t *__restrict__ a, int D, const uint32_t *__restrict__ b, int G,
-                                                          long words, int ntg, unsigned long long *__restrict__ inter)
-{
-    __shared__ unsigned int red[4][CT * CT];
-    const int ti = blockIdx.y / ntg, tj = blockIdx.y - ti * ntg;
-    unsigned int acc[CT][CT];
-#pragma unroll
-    for (int p = 0; p < CT; ++p)
-#pragma unroll
-        for (int q = 0; q < CT; ++q) acc[p][q] = 0u;
-    const long per = (words + gridDim.x - 1) / gridDim.x;
-    const long w0 = (long)blockIdx.x * per, w1 = w0 + per < words ? w0 + per : words;
-    for (long w = w0 + threadIdx.x; w < w1; w += 256) {
-        unsigned int va[CT], vb[CT];
-#pragma unroll
-        for (int p = 0; p < CT; ++p) {
-            const int i = ti * CT + p, j = tj * CT + p;
-            va[p] = i < D ? a[(long)i * words + w] : 0u;
-            vb[p] = j < G ? b[(long)j * words + w] : 0u;
-        }
-#pragma unroll
-        for (int p = 0; p < CT; ++p)
-#pragma unroll
-            for (int q = 0; q < CT; ++q) acc[p][q] += __popc(va[p] & vb[q]);
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int p = 0; p < CT; ++p)
-#pragma unroll
-        for (int q = 0; q < CT; ++q) {
-            unsigned int v = acc[p][q];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            if (lane == 0) red[wv][p * CT + q] = v;
-        }
-    __syncthreads();
-    if (threadIdx.x < CT * CT) {
-        const int p = threadIdx.x / CT, q = threadIdx.x % CT;
-        const int i = ti * CT + p, j = tj * CT + q;
-        const unsigned long long v = (unsigned long long)red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        if (i < D && j < G && v) atomicAdd(&inter[(long)i * G + j], v);
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -275,39 +215,11 @@ int s2d_rle_decode_bits(const int *ends, const long *run_off, const int *nrun, i
     return S2D_OK;
 }
 
-int s2d_mask_plane_areas_u32(const uint32_t *bits, int F, long words_per_plane, unsigned *area, hipStream_t stream)
-{
-    if (F < 0 || words_per_plane < 1) return S2D_ERR_ARG;
-    if (F == 0) return S2D_OK;
-    hipLaunchKernelGGL(plane_popcount_kernel, dim3(F), dim3(256), 0, stream, bits, words_per_plane, area);
-    S2D_CHECK_LAUNCH();
-    return S2D_OK;
-}
-
 int s2d_mask_plane_bbox_u32(const uint32_t *bits, int F, int H, int W, long words_per_plane, int *bbox, hipStream_t stream)
 {
     if (F < 0 || H < 1 || W < 1 || (long)H * W >= (1L << 31) || words_per_plane != ((long)H * W + 31) / 32) return S2D_ERR_ARG;
     if (F == 0) return S2D_OK;
     hipLaunchKernelGGL(plane_bbox_kernel, dim3(F), dim3(256), 0, stream, bits, H, W, words_per_plane, bbox);
-    S2D_CHECK_LAUNCH();
-    return S2D_OK;
-}
-
-int s2d_mask_cross_counts_u64(const uint32_t *a, int D, const uint32_t *b, int G, long words, unsigned long long *inter,
-                              hipStream_t stream)
-{
-    if (D < 0 || G < 0 || words < 0) return S2D_ERR_ARG;
-    if (D == 0 || G == 0) return S2D_OK;
-    if (s2d_zero_async(inter, sizeof(unsigned long long) * (size_t)D * G, stream) != S2D_OK) return S2D_ERR_LAUNCH;
-    if (words == 0) return S2D_OK;
-    const int ntd = (D + CT - 1) / CT, ntg = (G + CT - 1) / CT;
-    const long ntiles = (long)ntd * ntg;
-    if (ntiles >= 65536) return S2D_ERR_ARG;
-    int chunks = cdiv(words, 256 * 16);                 // >= 16 words per thread
-    const int want = cdiv(2048, ntiles);                // enough workgroups to fill 256 CUs
-    if (chunks > want) chunks = want;
-    if (chunks < 1) chunks = 1;
-    hipLaunchKernelGGL(cross_count_kernel, dim3(chunks, (unsigned)ntiles), dim3(256), 0, stream, a, D, b, G, words, ntg, inter);
     S2D_CHECK_LAUNCH();
     return S2D_OK;
 }

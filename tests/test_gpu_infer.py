@@ -1,5 +1,6 @@
-"""GPU parity of the eval-side step: inference_video on the HIP kernels of csrc/infer.hip vs the
-golden vectors from the reference's own inference_video and vs the CPU oracle, through the C ABI."""
+"""GPU parity of the eval-side step: inference_video on the HIP kernels of csrc/infer.hip and
+csrc/mask_counts.hip (pair counts) vs the golden vectors from the reference's own inference_video and vs the CPU oracle, through
+the C ABI."""
 import numpy as np
 import pytest
 import torch

@@ -76,12 +76,13 @@ def test_decode_matches_oracle(oracle, H, W):
         assert area[f] == ref.sum()
 
 
-@pytest.mark.parametrize("D,G", [(1, 1), (10, 5), (13, 9)])
-def test_cross_counts_match_pair_counts(D, G):
+# the last case is 9000 words per track: three chunks of the word range add into every entry (the others are one chunk)
+@pytest.mark.parametrize("D,G,T,H,W", [(1, 1, 3, 45, 70), (10, 5, 3, 45, 70), (13, 9, 3, 45, 70), (13, 9, 2, 360, 400)],
+                         ids=["1-1", "10-5", "13-9", "13-9-chunks"])
+def test_cross_counts_match_pair_counts(D, G, T, H, W):
     from s2d_amd import ops
     from s2d_amd.ytvis_eval import cross_counts
     rng = np.random.default_rng(D * 31 + G)
-    T, H, W = 3, 45, 70
     m = torch.from_numpy((rng.random((D + G, T, H, W)) < 0.3).astype(np.uint8)).to(DEV)
     bits = ops.pack_mask_bits(m.view(D + G, -1))
     got = cross_counts(bits[:D].contiguous(), bits[D:].contiguous()).cpu().numpy()
