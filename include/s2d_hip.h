@@ -636,6 +636,44 @@ int s2d_coco_match(const double *iou, const long *groups, int n_groups, const in
                    const double *area_rng, int A, int *dt_match, int *gt_match, int *dt_ignore, int *gt_ignore_out, int *gt_perm,
                    hipStream_t stream);
 
+/* ---- Ragged RLE decode and the image self-training merge (s2d_amd/rle_ragged.py, s2d_amd/selftrain.py, csrc/rle_ragged.hip; the
+ * reference's model_training/cutler/tools/get_self_training_ann.py).  The three calls above the keep rule are s2d_rle_parse_strings,
+ * s2d_rle_decode_bits and s2d_mask_plane_bbox_u32 for a CHUNK of P planes of different sizes, one launch each; they share the device
+ * bodies of those calls (csrc/rle_planes.h), so a plane comes out bit for bit as the fixed-size call writes it.
+ *
+ * Plane table.  plane is a DEVICE int64 table [P][4] = {word0, H, W, reserved 0}: plane p is H x W, row-major, in the
+ * s2d_rle_decode_bits layout, ceil(H*W/32) words from word word0 of ONE flat buffer `bits` of total_words words.  With the planes of
+ * an image back to back (its D planes, then its G planes) this is the COCO chunk layout above: s2d_coco_mask_iou_ragged reads the
+ * buffer through its own img / tiles tables without a copy.  The caller checks the table (H, W >= 1, H*W < 2^31, word ranges inside
+ * [0, total_words) and disjoint); a row that does not fit the buffer is skipped by the kernels (no read, no write; its box is 0,0,0,0).
+ * All four calls only enqueue: no allocation, no synchronisation.  P == 0 (N == 0) is a no-op that returns S2D_OK; a negative count or
+ * a null pointer returns S2D_ERR_ARG with nothing launched and nothing written. */
+
+/* s2d_rle_parse_strings with the clamp hw = H*W of string f taken from plane[f]: one wave per string; strings with nrun[f] < 0 on entry
+ * are parsed into ends[str_off[f] + j] and nrun[f] is set, the others (run ends already in place, or an absent plane with 0 runs) are
+ * left alone.  str_off DEVICE int64 [P+1]. */
+int s2d_rle_parse_ragged(const uint8_t *chars, const long *str_off, const long *plane, int P, int *ends, int *nrun, hipStream_t stream);
+
+/* s2d_rle_decode_bits for the chunk.  run_off DEVICE int64 [P+1] (plane f owns the slots run_off[f] .. run_off[f+1]; nrun[f] beyond
+ * them is cut).  tiles: DEVICE int32 [n_tiles][2] = {plane, column block of 256}; the host lists ceil(W/256) tiles for every plane,
+ * each once (a plane without a tile stays all zero).  One launch with a 1-D grid over the tiles: a wave walks 64 columns of
+ * its plane with that plane's H, W, word base and its own aligned = (W % 32 == 0) decision.  All total_words words of bits are zeroed
+ * by the call, words of no plane included.  tiles may be null when n_tiles == 0. */
+int s2d_rle_decode_ragged(const int *ends, const long *run_off, const int *nrun, const long *plane, int P, const int *tiles, int n_tiles,
+                          uint32_t *bits, long total_words, hipStream_t stream);
+
+/* s2d_mask_plane_bbox_u32 for the chunk: bbox [P][4] int = x, y, w, h of plane p (rleToBbox: the tight box), 0,0,0,0 for an empty
+ * plane.  One workgroup per plane. */
+int s2d_mask_plane_bbox_ragged_u32(const uint32_t *bits, const long *plane, int P, long total_words, int *bbox, hipStream_t stream);
+
+/* The keep rule of the self-training merge on the outputs of s2d_coco_mask_iou_ragged (same img table), for a chunk whose D side is
+ * the previous round's masks and whose G side is the kept predictions: keep[d] (int32, flat D numbering) = 1 iff EVERY g of the same
+ * image has 2 * inter < area_d + area_g - inter (int64), so 1 for an image with G == 0.  This is the reference's
+ * `iou_max < 0.5` on float32 inter / union, exactly, for images of fewer than 2^24 pixels; a pair with union == 0 (both masks empty)
+ * fails the test, as the reference's NaN does.  inter / area_d / area_g / keep may be null when the chunk has no such element. */
+int s2d_selftrain_keep_ragged(const long long *inter, const int *area_d, const int *area_g, const long *img, int N, int *keep,
+                              hipStream_t stream);
+
 /* ---- test-time frame resize (s2d_amd/data/resize.py, data/test_loader.py): detectron2 ResizeTransform.apply_image =
  * PIL Image.resize(BILINEAR) on uint8 RGB frames, bit-exact ------------------------------------------------------------- */
 

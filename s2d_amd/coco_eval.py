@@ -89,6 +89,44 @@ def _image_table(Ds, Gs):
     return img, dt0, gt0, pair0
 
 
+def chunk_tables(Ds, Gs, sizes):
+    """the host tables of a chunk whose image n has Ds[n] + Gs[n] planes of sizes[n] = (H, W), back to back in one flat buffer (the D
+    planes, then the G planes) -> (img int64 [N, 9], tiles int32 [n_tiles, 3], dt0, gt0, pair0, words): what
+    s2d_coco_mask_iou_ragged reads (include/s2d_hip.h, "Ragged layout"; max(1, ceil(D/8)) * max(1, ceil(G/8)) pair tiles for every
+    image with planes) and the buffer's length"""
+    img, dt0, gt0, pair0 = _image_table(Ds, Gs)
+    tiles, word = [], 0
+    for n, (H, W) in enumerate(sizes):
+        if H < 1 or W < 1 or H * W >= 1 << 31:
+            raise ValueError(f"image of {H}x{W}")
+        wpp = (H * W + 31) // 32
+        D, G = int(img[n, 4]), int(img[n, 5])
+        img[n, :4] = word, word + D * wpp, wpp, H * W
+        word += (D + G) * wpp
+        if D + G:
+            ntd, ntg = max(1, (D + 7) // 8), max(1, (G + 7) // 8)
+            tiles.append(np.stack([np.full(ntd * ntg, n), np.repeat(np.arange(ntd), ntg), np.tile(np.arange(ntg), ntd)], 1))
+    tiles_h = np.concatenate(tiles).astype(np.int32) if tiles else np.zeros((0, 3), np.int32)
+    return img, tiles_h, dt0, gt0, pair0, word
+
+
+def staged_chunk(bits, Ds, Gs, sizes, crowd, dev):
+    """-> the SimpleNamespace stage_planes documents, for a flat buffer `bits` (int32 CUDA [words], or None for a chunk without
+    planes) that already holds the chunk's planes in the layout of chunk_tables; crowd: uint8 [sum Gs].  The tables are uploaded once."""
+    img, tiles_h, dt0, gt0, pair0, word = chunk_tables(Ds, Gs, sizes)
+    crowd_h = np.asarray(crowd, np.uint8).reshape(-1)
+    if crowd_h.size != gt0[-1]:
+        raise ValueError("crowd flags do not match the ground-truth planes")
+    st = SimpleNamespace(bits=None, words=word, N=len(sizes), img=img, dt0=dt0, gt0=gt0, pair0=pair0, img_dev=None, tiles_dev=None,
+                         n_tiles=0, crowd_dev=None, dev=dev)
+    if len(tiles_h):
+        if bits is None or bits.dim() != 1 or bits.numel() != word:
+            raise ValueError(f"a buffer of {None if bits is None else tuple(bits.shape)} for a chunk of {word} words")
+        st.bits = bits
+        st.img_dev, st.tiles_dev, st.n_tiles, st.crowd_dev = _up(img, dev), _up(tiles_h, dev), len(tiles_h), _up(crowd_h, dev)
+    return st
+
+
 # --------------------------------------------------------------------------------------------------------------- device
 def stage_planes(planes, crowd, device=None):
     """the chunk's planes concatenated ONCE into the flat buffer the kernels read, and the tables uploaded once (arguments as
@@ -100,9 +138,8 @@ def stage_planes(planes, crowd, device=None):
     dev = _device(device)
     Ds = [0 if p[0] is None else int(p[0].shape[0]) for p in planes]
     Gs = [0 if p[1] is None else int(p[1].shape[0]) for p in planes]
-    img, dt0, gt0, pair0 = _image_table(Ds, Gs)
-    parts, tiles, word = [], [], 0
-    for n, (db, gb, H, W) in enumerate(planes):
+    parts = []
+    for db, gb, H, W in planes:
         wpp = (H * W + 31) // 32
         if H < 1 or W < 1 or H * W >= 1 << 31:
             raise ValueError(f"image of {H}x{W}")
@@ -113,23 +150,11 @@ def stage_planes(planes, crowd, device=None):
                     raise ValueError(f"planes of shape {tuple(b.shape)} for a {H}x{W} image ({wpp} words)")
                 if b.shape[0]:
                     parts.append(b.reshape(-1))
-        D, G = Ds[n], Gs[n]
-        img[n, :4] = word, word + D * wpp, wpp, H * W
-        word += (D + G) * wpp
-        if D + G:
-            ntd, ntg = max(1, (D + 7) // 8), max(1, (G + 7) // 8)
-            tiles.append(np.stack([np.full(ntd * ntg, n), np.repeat(np.arange(ntd), ntg), np.tile(np.arange(ntg), ntd)], 1))
-    crowd_h = np.concatenate([np.asarray(c, np.uint8).reshape(-1) for c in crowd]) if len(crowd) else np.zeros(0, np.uint8)
-    if len(crowd) != len(planes) or crowd_h.size != gt0[-1] or any(len(c) != g for c, g in zip(crowd, Gs)):
+    if len(crowd) != len(planes) or any(len(c) != g for c, g in zip(crowd, Gs)):
         raise ValueError("crowd flags do not match the ground-truth planes")
-    st = SimpleNamespace(bits=None, words=word, N=len(planes), img=img, dt0=dt0, gt0=gt0, pair0=pair0, img_dev=None, tiles_dev=None,
-                         n_tiles=0, crowd_dev=None, dev=dev)
-    if tiles:
-        tiles_h = np.concatenate(tiles).astype(np.int32)
-        st.bits = torch.cat(parts) if len(parts) > 1 else parts[0]
-        assert st.bits.numel() == word
-        st.img_dev, st.tiles_dev, st.n_tiles, st.crowd_dev = _up(img, dev), _up(tiles_h, dev), len(tiles_h), _up(crowd_h, dev)
-    return st
+    crowd_h = np.concatenate([np.asarray(c, np.uint8).reshape(-1) for c in crowd]) if len(crowd) else np.zeros(0, np.uint8)
+    bits = (torch.cat(parts) if len(parts) > 1 else parts[0]) if parts else None
+    return staged_chunk(bits, Ds, Gs, [(p[2], p[3]) for p in planes], crowd_h, dev)
 
 
 def mask_iou_staged(st, bits=None):

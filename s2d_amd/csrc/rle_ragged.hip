@@ -1,0 +1,150 @@
+// RLE parse, decode and tight boxes for a CHUNK of planes of different sizes, one launch each however many images the chunk holds
+// (s2d_amd/rle_ragged.py), and the keep rule of the image self-training merge (s2d_amd/selftrain.py; the reference's
+// model_training/cutler/tools/get_self_training_ann.py:161-166).  The per-plane bodies are those of the fixed-size entry points
+// (rle_planes.h; ytvis_eval.hip): here H, W and the word base of a plane come from its row of the plane table
+//
+//   plane int64 [P][4] = {word0, H, W, 0}     plane p: H x W, ceil(H*W/32) words from word word0 of the flat buffer
+//
+// which is the COCO chunk layout (include/s2d_hip.h, "Ragged layout"), so s2d_coco_mask_iou_ragged reads the decoded buffer in place.
+// A row the buffer cannot hold (H or W < 1, H*W >= 2^31, words outside [0, total_words)) is skipped by every kernel: nothing is read
+// or written for it.  The host checks the table before the call; the kernels do not rely on that.
+#include "rle_planes.h"
+
+namespace {
+
+struct PlaneRow {
+    long word0, wpp;
+    int H, W;
+    bool ok;
+};
+
+__device__ __forceinline__ PlaneRow plane_row(const long *__restrict__ plane, int p, long total_words)
+{
+    const long *r = plane + 4L * p;
+    PlaneRow q;
+    const long H = r[1], W = r[2];
+    q.word0 = r[0];
+    q.ok = H >= 1 && W >= 1 && H < (1L << 31) && W < (1L << 31) && H * W < (1L << 31);
+    q.H = (int)H; q.W = (int)W;
+    q.wpp = q.ok ? (H * W + 31) / 32 : 0;
+    q.ok = q.ok && q.word0 >= 0 && q.word0 <= total_words - q.wpp;
+    return q;
+}
+
+// rle_parse_kernel with the clamp taken from the plane's own size
+__global__ __launch_bounds__(RLE_PARSE_T) void rle_parse_ragged_kernel(const uint8_t *__restrict__ chars, const long *__restrict__ str_off,
+                                                                       const long *__restrict__ plane, int P, int *__restrict__ ends,
+                                                                       int *__restrict__ nrun)
+{
+    const int f = blockIdx.x * (RLE_PARSE_T / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (f >= P || nrun[f] >= 0) return;                     // whole waves
+    const long H = plane[4L * f + 1], W = plane[4L * f + 2];
+    const long hw = H >= 1 && W >= 1 && H < (1L << 31) && W < (1L << 31) && H * W < (1L << 31) ? H * W : 0;   // a bad row: every end 0
+    const long b = str_off[f];
+    const int m = rle_parse_string(chars + b, str_off[f + 1] - b, hw, ends + b, lane);
+    if (lane == 0) nrun[f] = m;
+}
+
+// tiles [n_tiles][2] = {plane, column block of 256}; one workgroup per tile, a wave per 64 columns.  bits must be zero on entry
+__global__ __launch_bounds__(RLE_DEC_T) void rle_decode_ragged_kernel(const int *__restrict__ ends, const long *__restrict__ run_off,
+                                                                      const int *__restrict__ nrun, const long *__restrict__ plane, int P,
+                                                                      const int *__restrict__ tiles, uint32_t *__restrict__ bits,
+                                                                      long total_words)
+{
+    const int f = tiles[2L * blockIdx.x], cb = tiles[2L * blockIdx.x + 1];
+    if (f < 0 || f >= P || cb < 0) return;
+    const PlaneRow q = plane_row(plane, f, total_words);
+    const long x0 = ((long)cb * (RLE_DEC_T / 64) + (threadIdx.x >> 6)) * 64;
+    if (!q.ok || x0 >= q.W) return;                         // whole waves
+    const long r0 = run_off[f];
+    int n = nrun[f];
+    const long cap = run_off[f + 1] - r0;                   // the plane's slots
+    n = n < 0 ? 0 : ((long)n > cap ? (int)cap : n);
+    rle_decode_columns(ends + r0, n, q.H, q.W, (int)x0, threadIdx.x & 63, bits + q.word0);
+}
+
+__global__ __launch_bounds__(256) void plane_bbox_ragged_kernel(const uint32_t *__restrict__ bits, const long *__restrict__ plane,
+                                                                long total_words, int *__restrict__ bbox)
+{
+    const PlaneRow q = plane_row(plane, blockIdx.x, total_words);     // uniform over the workgroup
+    int *b = bbox + 4L * blockIdx.x;
+    if (!q.ok) {
+        if (threadIdx.x < 4) b[threadIdx.x] = 0;
+        return;
+    }
+    plane_tight_box(bits + q.word0, q.H, q.W, q.wpp, b);
+}
+
+constexpr int KEEP_T = 64;
+
+// one workgroup (a wave) per image, a thread per previous-round mask d: keep[dt0 + d] = every g has 2 * inter < union
+__global__ __launch_bounds__(KEEP_T) void selftrain_keep_kernel(const long long *__restrict__ inter, const int *__restrict__ area_d,
+                                                                const int *__restrict__ area_g, const long *__restrict__ img,
+                                                                int *__restrict__ keep)
+{
+    const long *r = img + 9L * blockIdx.x;
+    const long D = r[4], G = r[5], dt0 = r[6], gt0 = r[7], pair0 = r[8];
+    for (long d = threadIdx.x; d < D; d += KEEP_T) {
+        const long ad = area_d[dt0 + d];
+        int k = 1;
+        for (long g = 0; g < G; ++g) {
+            const long i = inter[pair0 + d * G + g];
+            const long u = ad + (long)area_g[gt0 + g] - i;
+            if (!(2 * i < u)) k = 0;                        // iou >= 0.5, or u == 0 (the reference's NaN < 0.5 is false)
+        }
+        keep[dt0 + d] = k;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int s2d_rle_parse_ragged(const uint8_t *chars, const long *str_off, const long *plane, int P, int *ends, int *nrun, hipStream_t stream)
+{
+    if (P < 0) return S2D_ERR_ARG;
+    if (P == 0) return S2D_OK;
+    if (!chars || !str_off || !plane || !ends || !nrun) return S2D_ERR_ARG;
+    hipLaunchKernelGGL(rle_parse_ragged_kernel, dim3(cdiv(P, RLE_PARSE_T / 64)), dim3(RLE_PARSE_T), 0, stream, chars, str_off, plane, P,
+                       ends, nrun);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_rle_decode_ragged(const int *ends, const long *run_off, const int *nrun, const long *plane, int P, const int *tiles, int n_tiles,
+                          uint32_t *bits, long total_words, hipStream_t stream)
+{
+    if (P < 0 || n_tiles < 0 || total_words < 0) return S2D_ERR_ARG;
+    if (P == 0) return S2D_OK;
+    if (!ends || !run_off || !nrun || !plane || !bits || (n_tiles && !tiles)) return S2D_ERR_ARG;
+    if (total_words && s2d_zero_async(bits, sizeof(uint32_t) * (size_t)total_words, stream) != S2D_OK) return S2D_ERR_LAUNCH;
+    if (n_tiles == 0 || total_words == 0) return S2D_OK;
+    hipLaunchKernelGGL(rle_decode_ragged_kernel, dim3(n_tiles), dim3(RLE_DEC_T), 0, stream, ends, run_off, nrun, plane, P, tiles, bits,
+                       total_words);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_mask_plane_bbox_ragged_u32(const uint32_t *bits, const long *plane, int P, long total_words, int *bbox, hipStream_t stream)
+{
+    if (P < 0 || total_words < 0) return S2D_ERR_ARG;
+    if (P == 0) return S2D_OK;
+    if (!bits || !plane || !bbox) return S2D_ERR_ARG;
+    hipLaunchKernelGGL(plane_bbox_ragged_kernel, dim3(P), dim3(256), 0, stream, bits, plane, total_words, bbox);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_selftrain_keep_ragged(const long long *inter, const int *area_d, const int *area_g, const long *img, int N, int *keep,
+                              hipStream_t stream)
+{
+    if (N < 0) return S2D_ERR_ARG;
+    if (N == 0) return S2D_OK;
+    if (!img) return S2D_ERR_ARG;
+    hipLaunchKernelGGL(selftrain_keep_kernel, dim3(N), dim3(KEEP_T), 0, stream, inter, area_d, area_g, img, keep);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+}  // extern "C"
