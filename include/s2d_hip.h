@@ -450,6 +450,29 @@ int s2d_infer_index_u8(const float *mask_logits, int ldq, int T, int hm, int wm,
  * direct path; -1: the sizes are refused */
 long s2d_infer_index_lds_bytes(int ldq, int T, int hm, int wm, int Hp, int Wp, int ih, int iw, int oh, int ow, int K);
 
+/* Stage-1 frame masks (s2d_amd/keymask/frame_masks.py; cutler/demo/predictor.py:237-355 overlay_masks_numpy), plane-free.  With
+ * m_k,t = "proposal k holds the pixel", the bit s2d_infer_masks_u8 / s2d_infer_index_u8 form (same device functions, same float32
+ * expression tree, v > 0; NaN and -0.0 hold nothing):
+ *   areas int32 [K][T] (zeroed by the call) = set pixels of m_k,t at output size;
+ *   order int32 [T][K] (may be NULL) = per frame the proposals in descending area, equal areas in proposal order: the stable sort
+ *   s2d_mask_frame_areas_i32 documents, written by a follow-up launch of the same ranking kernel.
+ * Same geometry, limits and refusals as s2d_infer_index_u8 (1 <= K <= 254, ldq <= 128 and a multiple of 4, query clamped); no
+ * workspace, nothing of size [K][T][oh][ow].  Every proposal is evaluated at every pixel; a workgroup adds its tile's count once
+ * per (k, t) with an integer atomic, so a second call gives the same bits.  Bad arguments: S2D_ERR_ARG, nothing launched. */
+int s2d_infer_frame_areas_i32(const float *mask_logits, int ldq, int T, int hm, int wm, int Hp, int Wp, int ih, int iw,
+                              int oh, int ow, const int *query, int K, int *areas, int *order, hipStream_t stream);
+
+/* The paint pass: each frame starts black and the proposals are painted in order[t][0], order[t][1], ..., a later one over an
+ * earlier one; so a pixel belongs to the holder with the LARGEST position in order[t] (with s2d_infer_frame_areas_i32's order: the
+ * smallest area, among equal areas the higher k).  rgb u8 [T][oh][ow][3] = colors[k] (u8 [K][3]; by k, not by position) of that
+ * owner or (0,0,0); index u8 [T][oh][ow] (may be NULL) = k + 1 of that owner or 0.  Every byte of both is written, at any alignment
+ * (12 bytes of four pixels as three dwords where the address allows); 64-bit output offsets.  An order entry outside [0, K) is
+ * clamped into it: a row that is no permutation gives unspecified colours and no out-of-range access.  Limits and refusals as
+ * s2d_infer_index_u8. */
+int s2d_infer_paint_u8(const float *mask_logits, int ldq, int T, int hm, int wm, int Hp, int Wp, int ih, int iw,
+                       int oh, int ow, const int *query, int K, const int *order, const uint8_t *colors,
+                       uint8_t *rgb, uint8_t *index, hipStream_t stream);
+
 /* byte mask planes u8 [K][n] (0 / non-0) -> bit words [K][ceil(n/32)] in the layout above: feeds s2d_mask_pair_counts_u64 for
  * masks that exist as bytes -- the distillation pseudo targets under MODEL.MASK_FORMER.DISTILLATION_NMS
  * (kd_video_maskformer_model.py:484-520). */

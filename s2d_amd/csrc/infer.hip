@@ -16,6 +16,7 @@
 // intersection counts, from which the host runs the greedy loop without touching the masks again.
 #include "common.h"
 #include "class_select.h"
+#include "draw_order.h"
 
 namespace {
 
@@ -277,16 +278,128 @@ __host__ __device__ __forceinline__ int win_hi(float s1, float s2, int dst, int 
     return i1;
 }
 
-struct IndexParams {
+// four labels of one tile row: one dword where the address allows, else nx bytes
+__device__ __forceinline__ void store_labels(uint8_t *o, const unsigned int (&lab)[4], int nx)
+{
+    if (nx == 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0)
+        *reinterpret_cast<uint32_t *>(o) = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
+    else
+        for (int j = 0; j < nx; ++j) o[j] = (uint8_t)lab[j];
+}
+
+// What the tiled kernels (index maps, frame areas, paint) share of one call: the logits, the selection and the geometry that
+// index_geometry fills.
+struct TileParams {
     const float *ml;           // [T*hm*wm][ldq]
     const int *query;          // [K]
-    const float *score;        // [K] (rule 1)
-    uint8_t *index;            // [T][oh][ow]
-    int ldq, T, hm, wm, ih, iw, oh, ow, K, rule;
+    int ldq, T, hm, wm, ih, iw, oh, ow, K;
     int tiles_x, tiles_y;
     int cap;                   // window pixels the dynamic LDS holds per proposal (0: every workgroup reads directly)
     float s1y, s1x, s2y, s2x;
 };
+
+struct IndexParams : TileParams {
+    const float *score;        // [K] (rule 1)
+    uint8_t *index;            // [T][oh][ow]
+    int rule;
+};
+
+struct AreaParams : TileParams {
+    int *areas;                // [K][T], zero before the launch
+};
+
+struct PaintParams : TileParams {
+    const int *order;          // [T][K]
+    const uint8_t *colors;     // [K][3]
+    uint8_t *rgb;              // [T][oh][ow][3]
+    uint8_t *index;            // [T][oh][ow] or null
+};
+
+// The tile of blockIdx.x and the low-resolution window under it (workgroup-uniform)
+struct TileWindow {
+    int t, y0, x0;             // frame, first output row / column of the tile
+    int rlo, clo, ww, np;      // first window row / column, window width, window pixels
+    bool staged;               // the window fits the dynamic LDS: the taps are LDS reads, else reads of the logits themselves
+    const float *frame;        // the frame's logits [hm*wm][ldq]
+};
+
+template <bool SAME>
+__device__ __forceinline__ TileWindow tile_window(const TileParams &p)
+{
+    TileWindow w;
+    const unsigned int per_frame = (unsigned int)p.tiles_x * (unsigned int)p.tiles_y;
+    w.t = (int)(blockIdx.x / per_frame);
+    const unsigned int rem = blockIdx.x - (unsigned int)w.t * per_frame;
+    const int ty = (int)(rem / (unsigned int)p.tiles_x), tx = (int)(rem - (unsigned int)ty * (unsigned int)p.tiles_x);
+    w.y0 = ty * IX_TH; w.x0 = tx * IX_TW;
+    const int ylast = (w.y0 + IX_TH < p.oh ? w.y0 + IX_TH : p.oh) - 1, xlast = (w.x0 + IX_TW < p.ow ? w.x0 + IX_TW : p.ow) - 1;
+    // the window; clamped to the map so that no tap arithmetic, however it rounds, makes the gather read outside the logits
+    w.rlo = win_lo<SAME>(p.s1y, p.s2y, w.y0, p.hm, p.ih); w.clo = win_lo<SAME>(p.s1x, p.s2x, w.x0, p.wm, p.iw);
+    int rhi = win_hi<SAME>(p.s1y, p.s2y, ylast, p.hm, p.ih), chi = win_hi<SAME>(p.s1x, p.s2x, xlast, p.wm, p.iw);
+    if (rhi > p.hm - 1) rhi = p.hm - 1;
+    if (chi > p.wm - 1) chi = p.wm - 1;
+    w.ww = chi - w.clo + 1;
+    w.np = (rhi - w.rlo + 1) * w.ww;
+    w.staged = w.np >= 1 && w.np <= p.cap;
+    w.frame = p.ml + (long)w.t * p.hm * p.wm * p.ldq;
+    return w;
+}
+
+// qs[k] = query[k] clamped into [0, ldq); staged: win[k][window pixel] = that column of the logits under the tile.  Every thread
+// of the workgroup calls it; what the caller wrote to LDS before the call is visible after it.
+__device__ __forceinline__ void stage_window(const TileParams &p, const TileWindow &w, int *qs, float *win)
+{
+    for (int k = threadIdx.x; k < p.K; k += 256) {
+        int q = p.query[k];
+        qs[k] = q < 0 ? 0 : (q > p.ldq - 1 ? p.ldq - 1 : q);
+    }
+    __syncthreads();
+    if (w.staged) {
+        for (int idx = threadIdx.x; idx < w.np * p.K; idx += 256) {
+            const int pp = idx / p.K, k = idx - pp * p.K;
+            const int wr = pp / w.ww, wc = pp - wr * w.ww;
+            win[k * w.np + pp] = w.frame[((long)(w.rlo + wr) * p.wm + (w.clo + wc)) * p.ldq + qs[k]];
+        }
+        __syncthreads();
+    }
+}
+
+// The taps of a thread's 4 consecutive pixels (y, xb .. xb + 3) of one tile row, (y, xb) inside the frame
+struct PixelTaps {
+    RowTaps r;
+    ColTaps c[4];
+    long oa0, oa1, ob0, ob1;   // element offsets of the four rows inside one proposal's plane (staged) or the frame's logits (direct)
+    int nx;                    // pixels of the four inside the frame
+};
+
+template <bool SAME>
+__device__ __forceinline__ PixelTaps pixel_taps(const TileParams &p, const TileWindow &w, int y, int xb)
+{
+    PixelTaps t;
+    t.nx = p.ow - xb < 4 ? p.ow - xb : 4;
+    t.r = row_taps<SAME>(p.s1y, p.s2y, y, p.hm, p.ih);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)                         // a column past the frame edge repeats the last one; its result is not stored
+        t.c[j] = col_taps<SAME>(p.s1x, p.s2x, xb + (j < t.nx ? j : t.nx - 1), p.wm, p.iw, w.staged ? w.clo : 0, w.staged ? 1 : p.ldq);
+    const long rs = w.staged ? (long)w.ww : (long)p.wm * p.ldq;
+    const int ro = w.staged ? w.rlo : 0;
+    t.oa0 = (t.r.qa0 - ro) * rs; t.oa1 = (t.r.qa1 - ro) * rs;
+    t.ob0 = SAME ? 0 : (t.r.qb0 - ro) * rs; t.ob1 = SAME ? 0 : (t.r.qb1 - ro) * rs;
+    return t;
+}
+
+// where proposal k's taps are read from: its staged plane, or its column of the frame's logits
+__device__ __forceinline__ const float *proposal_base(const TileWindow &w, const float *win, const int *qs, int k)
+{
+    return w.staged ? win + k * w.np : w.frame + qs[k];
+}
+
+// resize_value of proposal `base` at pixel j of the thread's four
+template <bool SAME>
+__device__ __forceinline__ float pixel_value(const float *__restrict__ base, const PixelTaps &t, int j)
+{
+    return resize_value<SAME>(base + t.oa0, base + t.oa1, base + t.ob0, base + t.ob1, t.r, t.c[j]);
+}
 
 template <bool SAME>
 __global__ __launch_bounds__(256) void infer_index_kernel(IndexParams p)
@@ -294,66 +407,28 @@ __global__ __launch_bounds__(256) void infer_index_kernel(IndexParams p)
     extern __shared__ float win[];                      // [K][wh*ww]
     __shared__ int qs[IX_KMAX];
     __shared__ float ss[IX_KMAX];
-    const unsigned int per_frame = (unsigned int)p.tiles_x * (unsigned int)p.tiles_y;
-    const int t = (int)(blockIdx.x / per_frame);
-    const unsigned int rem = blockIdx.x - (unsigned int)t * per_frame;
-    const int ty = (int)(rem / (unsigned int)p.tiles_x), tx = (int)(rem - (unsigned int)ty * (unsigned int)p.tiles_x);
-    const int y0 = ty * IX_TH, x0 = tx * IX_TW;
-    const int ylast = (y0 + IX_TH < p.oh ? y0 + IX_TH : p.oh) - 1, xlast = (x0 + IX_TW < p.ow ? x0 + IX_TW : p.ow) - 1;
-    // the window; clamped to the map so that no tap arithmetic, however it rounds, makes the gather read outside the logits
-    const int rlo = win_lo<SAME>(p.s1y, p.s2y, y0, p.hm, p.ih), clo = win_lo<SAME>(p.s1x, p.s2x, x0, p.wm, p.iw);
-    int rhi = win_hi<SAME>(p.s1y, p.s2y, ylast, p.hm, p.ih), chi = win_hi<SAME>(p.s1x, p.s2x, xlast, p.wm, p.iw);
-    if (rhi > p.hm - 1) rhi = p.hm - 1;
-    if (chi > p.wm - 1) chi = p.wm - 1;
-    const int wh = rhi - rlo + 1, ww = chi - clo + 1, np = wh * ww;
-    const bool staged = np >= 1 && np <= p.cap;         // workgroup-uniform
+    const TileWindow w = tile_window<SAME>(p);
+    for (int k = threadIdx.x; k < p.K; k += 256) ss[k] = p.rule ? p.score[k] : 0.f;
+    stage_window(p, w, qs, win);
 
-    for (int k = threadIdx.x; k < p.K; k += 256) {
-        int q = p.query[k];
-        q = q < 0 ? 0 : (q > p.ldq - 1 ? p.ldq - 1 : q);
-        qs[k] = q;
-        ss[k] = p.rule ? p.score[k] : 0.f;
-    }
-    __syncthreads();
-    const float *frame = p.ml + (long)t * p.hm * p.wm * p.ldq;
-    if (staged) {
-        for (int idx = threadIdx.x; idx < np * p.K; idx += 256) {
-            const int pp = idx / p.K, k = idx - pp * p.K;
-            const int wr = pp / ww, wc = pp - wr * ww;
-            win[k * np + pp] = frame[((long)(rlo + wr) * p.wm + (clo + wc)) * p.ldq + qs[k]];
-        }
-        __syncthreads();
-    }
-
-    const int y = y0 + (int)(threadIdx.x >> 4), xb = x0 + (int)(threadIdx.x & 15) * 4;
+    const int y = w.y0 + (int)(threadIdx.x >> 4), xb = w.x0 + (int)(threadIdx.x & 15) * 4;
     if (y >= p.oh || xb >= p.ow) return;
-    const int nx = p.ow - xb < 4 ? p.ow - xb : 4;
-    const RowTaps r = row_taps<SAME>(p.s1y, p.s2y, y, p.hm, p.ih);
-    ColTaps c[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)                         // a column past the frame edge repeats the last one; its label is not stored
-        c[j] = col_taps<SAME>(p.s1x, p.s2x, xb + (j < nx ? j : nx - 1), p.wm, p.iw, staged ? clo : 0, staged ? 1 : p.ldq);
-    // element offsets of the four rows inside one proposal's plane (staged) or inside the frame's logits (direct)
-    const long rs = staged ? (long)ww : (long)p.wm * p.ldq;
-    const int ro = staged ? rlo : 0;
-    const long oa0 = (r.qa0 - ro) * rs, oa1 = (r.qa1 - ro) * rs;
-    const long ob0 = SAME ? 0 : (r.qb0 - ro) * rs, ob1 = SAME ? 0 : (r.qb1 - ro) * rs;
+    const PixelTaps px = pixel_taps<SAME>(p, w, y, xb);
 
     unsigned int lab[4] = {0u, 0u, 0u, 0u};
     float best[4] = {0.f, 0.f, 0.f, 0.f};
     for (int k = 0; k < p.K; ++k) {
-        const float *base = staged ? win + k * np : frame + qs[k];
-        const float *a0 = base + oa0, *a1 = base + oa1, *b0 = base + ob0, *b1 = base + ob1;
+        const float *base = proposal_base(w, win, qs, k);
         if (p.rule == 0) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                if (lab[j] == 0u && resize_value<SAME>(a0, a1, b0, b1, r, c[j]) > 0.f) lab[j] = (unsigned int)k + 1u;
+                if (lab[j] == 0u && pixel_value<SAME>(base, px, j) > 0.f) lab[j] = (unsigned int)k + 1u;
             if (lab[0] && lab[1] && lab[2] && lab[3]) break;
         } else {
             const float s = ss[k];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float v = resize_value<SAME>(a0, a1, b0, b1, r, c[j]);
+                const float v = pixel_value<SAME>(base, px, j);
                 if (v > 0.f) {
                     const float pr = s / (1.f + expf(-v));
                     if (lab[j] == 0u || pr > best[j]) { lab[j] = (unsigned int)k + 1u; best[j] = pr; }
@@ -361,16 +436,108 @@ __global__ __launch_bounds__(256) void infer_index_kernel(IndexParams p)
             }
         }
     }
-    uint8_t *o = p.index + ((long)t * p.oh + y) * p.ow + xb;
-    if (nx == 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0)
-        *reinterpret_cast<uint32_t *>(o) = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
-    else
-        for (int j = 0; j < nx; ++j) o[j] = (uint8_t)lab[j];
+    store_labels(p.index + ((long)w.t * p.oh + y) * p.ow + xb, lab, px.nx);
+}
+
+// ---- stage-1 frame masks (keymask/frame_masks.py): the paint rule of the reference's overlay_masks_numpy, plane-free -------------
+//
+// The reference (cutler/demo/predictor.py:237-355) sorts a frame's instances by descending mask area and paints them on black
+// in that order, each in the colour of its own index, so the smallest holder of a pixel shows.  Two kernels on the index kernel's
+// tile scheme (same window, staging and taps: tile_window / stage_window / pixel_taps above, so "proposal k holds the pixel" is the
+// bit s2d_infer_masks_u8 writes):
+//
+//  areas  every proposal at every pixel of the tile (no early exit: a covered pixel still counts); the holders of a wave are
+//         counted per pixel slot with a ballot and a popcount -- scalar instructions -- and lane 0 writes the wave's count of
+//         proposal k to cnt[wave][k]; after the loop one integer atomicAdd per (k, t) and workgroup, skipped for a count of 0.
+//         Integer sums do not depend on the order of the adds, so a second call gives the same bits.
+//  paint  the frame's draw order in LDS, walked from the last position (painted last, on top) to the first; the first holder met
+//         owns the pixel, and a thread leaves the loop when its four pixels are owned, as rule 0 of the index kernel does.
+//
+// Registers and LDS: areas 87 VGPRs two-stage (5 waves per SIMD; 64 for SAME) and 5 KB of static LDS (qs, cnt) beside the staged
+// window; paint 124 VGPRs two-stage (4 waves per SIMD; 60 for SAME) and 2 KB (qs, ord).  Registers bound occupancy below 18 KB of
+// staging; at the 40 KB limit three workgroups of either fit a CU, as for the index kernel.
+template <bool SAME>
+__global__ __launch_bounds__(256) void infer_frame_areas_kernel(AreaParams p)
+{
+    extern __shared__ float win[];                      // [K][wh*ww]
+    __shared__ int qs[IX_KMAX];
+    __shared__ int cnt[4][IX_KMAX];                     // [wave][k]
+    const TileWindow w = tile_window<SAME>(p);
+    stage_window(p, w, qs, win);
+
+    // no thread leaves before the barrier below: one outside the frame forms the taps of the tile's first pixel and counts nothing
+    const int y = w.y0 + (int)(threadIdx.x >> 4), xb = w.x0 + (int)(threadIdx.x & 15) * 4;
+    const bool inside = y < p.oh && xb < p.ow;
+    const PixelTaps px = pixel_taps<SAME>(p, w, inside ? y : w.y0, inside ? xb : w.x0);
+    const int n = inside ? px.nx : 0;
+    const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    for (int k = 0; k < p.K; ++k) {
+        const float *base = proposal_base(w, win, qs, k);
+        int c = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float v = pixel_value<SAME>(base, px, j);
+            c += __popcll(__ballot(j < n && v > 0.f));
+        }
+        if (lane == 0) cnt[wave][k] = c;
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < p.K; k += 256) {
+        const int c = cnt[0][k] + cnt[1][k] + cnt[2][k] + cnt[3][k];
+        if (c) atomicAdd(&p.areas[(long)k * p.T + w.t], c);
+    }
+}
+
+template <bool SAME>
+__global__ __launch_bounds__(256) void infer_paint_kernel(PaintParams p)
+{
+    extern __shared__ float win[];                      // [K][wh*ww]
+    __shared__ int qs[IX_KMAX];
+    __shared__ int ord[IX_KMAX];
+    const TileWindow w = tile_window<SAME>(p);
+    for (int r = threadIdx.x; r < p.K; r += 256) {      // an entry outside [0, K) is clamped: nothing is read out of range
+        const int k = p.order[(long)w.t * p.K + r];
+        ord[r] = k < 0 ? 0 : (k > p.K - 1 ? p.K - 1 : k);
+    }
+    stage_window(p, w, qs, win);
+
+    const int y = w.y0 + (int)(threadIdx.x >> 4), xb = w.x0 + (int)(threadIdx.x & 15) * 4;
+    if (y >= p.oh || xb >= p.ow) return;
+    const PixelTaps px = pixel_taps<SAME>(p, w, y, xb);
+
+    unsigned int own[4] = {0u, 0u, 0u, 0u};
+    for (int r = p.K - 1; r >= 0; --r) {
+        const int k = ord[r];
+        const float *base = proposal_base(w, win, qs, k);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (own[j] == 0u && pixel_value<SAME>(base, px, j) > 0.f) own[j] = (unsigned int)k + 1u;
+        if (own[0] && own[1] && own[2] && own[3]) break;
+    }
+
+    uint32_t wd[3] = {0u, 0u, 0u};                      // the 12 bytes of the four pixels
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (own[j]) {
+            const uint8_t *col = p.colors + 3 * (own[j] - 1u);
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) wd[(3 * j + ch) >> 2] |= (uint32_t)col[ch] << (8 * ((3 * j + ch) & 3));
+        }
+    const long pix = ((long)w.t * p.oh + y) * p.ow + xb;
+    uint8_t *o = p.rgb + pix * 3;
+    if (px.nx == 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+        reinterpret_cast<uint32_t *>(o)[0] = wd[0];
+        reinterpret_cast<uint32_t *>(o)[1] = wd[1];
+        reinterpret_cast<uint32_t *>(o)[2] = wd[2];
+    } else {
+        for (int b = 0; b < 3 * px.nx; ++b) o[b] = (uint8_t)(wd[b >> 2] >> (8 * (b & 3)));
+    }
+    if (p.index) store_labels(p.index + pix, own, px.nx);
 }
 
 // largest window (pixels) of any tile, from the same tap functions the kernel evaluates
 template <bool SAME>
-long index_max_window(const IndexParams &p)
+long index_max_window(const TileParams &p)
 {
     int mh = 0, mw = 0;
     for (int ty = 0; ty < p.tiles_y; ++ty) {
@@ -443,8 +610,9 @@ int s2d_infer_masks_u8(const float *mask_logits, int ldq, int T, int hm, int wm,
     return S2D_OK;
 }
 
-// geometry of one s2d_infer_index_u8 call -> p (pointers and rule left alone); false: the sizes are refused
-static bool index_geometry(IndexParams &p, int ldq, int T, int hm, int wm, int Hp, int Wp, int ih, int iw, int oh, int ow, int K)
+// geometry of one tiled call (s2d_infer_index_u8, s2d_infer_frame_areas_i32, s2d_infer_paint_u8) -> p (pointers left alone); false:
+// the sizes are refused
+static bool index_geometry(TileParams &p, int ldq, int T, int hm, int wm, int Hp, int Wp, int ih, int iw, int oh, int ow, int K)
 {
     if (K < 1 || K > IX_KMAX || ldq < 4 || ldq > 128 || (ldq & 3)) return false;
     if (T < 1 || hm < 1 || wm < 1 || ih < 1 || iw < 1 || ih > Hp || iw > Wp || oh < 1 || ow < 1) return false;
@@ -460,7 +628,7 @@ static bool index_geometry(IndexParams &p, int ldq, int T, int hm, int wm, int H
 
 long s2d_infer_index_lds_bytes(int ldq, int T, int hm, int wm, int Hp, int Wp, int ih, int iw, int oh, int ow, int K)
 {
-    IndexParams p;
+    TileParams p;
     if (!index_geometry(p, ldq, T, hm, wm, Hp, Wp, ih, iw, oh, ow, K)) return -1;
     return (long)p.cap * K * (long)sizeof(float);
 }
@@ -477,6 +645,38 @@ int s2d_infer_index_u8(const float *mask_logits, int ldq, int T, int hm, int wm,
     const size_t lds = (size_t)p.cap * K * sizeof(float);
     if (same) hipLaunchKernelGGL(infer_index_kernel<true>, dim3((unsigned int)nblocks), dim3(256), lds, stream, p);
     else hipLaunchKernelGGL(infer_index_kernel<false>, dim3((unsigned int)nblocks), dim3(256), lds, stream, p);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_infer_frame_areas_i32(const float *mask_logits, int ldq, int T, int hm, int wm, int Hp, int Wp, int ih, int iw, int oh, int ow,
+                              const int *query, int K, int *areas, int *order, hipStream_t stream)
+{
+    if (!mask_logits || !query || !areas) return S2D_ERR_ARG;
+    AreaParams p;
+    if (!index_geometry(p, ldq, T, hm, wm, Hp, Wp, ih, iw, oh, ow, K)) return S2D_ERR_ARG;
+    p.ml = mask_logits; p.query = query; p.areas = areas;
+    if (s2d_zero_async(areas, sizeof(int) * (size_t)K * T, stream) != S2D_OK) return S2D_ERR_LAUNCH;
+    const long nblocks = (long)T * p.tiles_x * p.tiles_y;
+    const size_t lds = (size_t)p.cap * K * sizeof(float);
+    if (ih == oh && iw == ow) hipLaunchKernelGGL(infer_frame_areas_kernel<true>, dim3((unsigned int)nblocks), dim3(256), lds, stream, p);
+    else hipLaunchKernelGGL(infer_frame_areas_kernel<false>, dim3((unsigned int)nblocks), dim3(256), lds, stream, p);
+    if (order) hipLaunchKernelGGL(draw_order_kernel, dim3(T), dim3(256), 0, stream, areas, K, T, order);   // K <= 254 threads rank
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_infer_paint_u8(const float *mask_logits, int ldq, int T, int hm, int wm, int Hp, int Wp, int ih, int iw, int oh, int ow,
+                       const int *query, int K, const int *order, const uint8_t *colors, uint8_t *rgb, uint8_t *index, hipStream_t stream)
+{
+    if (!mask_logits || !query || !order || !colors || !rgb) return S2D_ERR_ARG;
+    PaintParams p;
+    if (!index_geometry(p, ldq, T, hm, wm, Hp, Wp, ih, iw, oh, ow, K)) return S2D_ERR_ARG;
+    p.ml = mask_logits; p.query = query; p.order = order; p.colors = colors; p.rgb = rgb; p.index = index;
+    const long nblocks = (long)T * p.tiles_x * p.tiles_y;
+    const size_t lds = (size_t)p.cap * K * sizeof(float);
+    if (ih == oh && iw == ow) hipLaunchKernelGGL(infer_paint_kernel<true>, dim3((unsigned int)nblocks), dim3(256), lds, stream, p);
+    else hipLaunchKernelGGL(infer_paint_kernel<false>, dim3((unsigned int)nblocks), dim3(256), lds, stream, p);
     S2D_CHECK_LAUNCH();
     return S2D_OK;
 }

@@ -11,6 +11,7 @@
 // set does it read the 4 bytes above and below and the byte on each side, which its neighbours read as their own centre words,
 // so those come from L1 / L2 and every mask byte leaves HBM about once.
 #include "common.h"
+#include "draw_order.h"
 
 namespace {
 
@@ -41,20 +42,6 @@ __global__ __launch_bounds__(256) void plane_areas_kernel(const uint8_t *__restr
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(&areas[p], c);
-}
-
-// order[t][r] = the instance of rank r in frame t: rank = #{j : a_j > a_k or (a_j == a_k and j < k)}, a stable descending sort
-__global__ __launch_bounds__(256) void draw_order_kernel(const int *__restrict__ areas, int K, int T, int *__restrict__ order)
-{
-    __shared__ int a[256];
-    const int t = blockIdx.x, k = threadIdx.x;
-    if (k < K) a[k] = areas[(long)k * T + t];
-    __syncthreads();
-    if (k >= K) return;
-    const int ak = a[k];
-    int r = 0;
-    for (int j = 0; j < K; ++j) r += (a[j] > ak) | ((a[j] == ak) & (j < k));
-    order[(long)t * K + r] = k;
 }
 
 // 4 bytes of a row from x0 on; bytes at x >= W read as 0.  VEC: W % 4 == 0 and the row 4-byte aligned.

@@ -6,6 +6,9 @@
                                   or --tracker block-live [--tracker-options search=48,refresh=-1]: wide search, live template;
                                   or --tracker block-zm [--tracker-options search=48,texture=0]: zero-mean cost, texture gate)
 
+The mask tree M/<video>/<frame>.png is stage 1's output: `python -m s2d_amd.keymask.frame_masks` writes it from a checkpoint of this
+project (any other tree of one colour PNG per frame, such as the reference's cutler/demo output, reads the same).
+
 Restates keymask_ident/main_keymask_ident.py and its per-video stages with their file names, layouts, JSON contents and
 observable quirks:
 

@@ -265,6 +265,7 @@ class KDVideoMaskFormer(nn.Module):
         self.inference_rle = False                  # eval branch: pred_masks as COCO RLE lists encoded on the device (inference_video rle=True)
         self.inference_device_masks = False         # eval branch: pred_masks as the CUDA u8 [K,T,H,W] tensor (inference_video device_masks=True)
         self.inference_index = None                 # eval branch: a dict -> pred_masks as ONE CUDA u8 [T,H,W] proposal index map (inference_video index_map=...)
+        self.inference_paint = None                 # eval branch: a dict -> pred_masks as the stage-1 RGB picture u8 [T,H,W,3] (inference_video paint=...)
         self._side_delay_cycles = 0                 # tests only: spin the side stream this many cycles before the GT criterion
 
     @classmethod
@@ -639,16 +640,21 @@ class KDVideoMaskFormer(nn.Module):
         net = self.student if self.eval_student else self.teacher
         return _inference(net, images, batched_inputs, self.num_predictions_inference, self.use_nms, self.nms_threshold,
                           rle=getattr(self, "inference_rle", False), device_masks=getattr(self, "inference_device_masks", False),
-                          window=self._window(), owner=self, index_map=getattr(self, "inference_index", None))
+                          window=self._window(), owner=self, index_map=getattr(self, "inference_index", None),
+                          paint=getattr(self, "inference_paint", None))
 
     def _window(self):
         return (self.window_size, self.window_overlap) if self.window_inference else None
 
 
 def _inference(net, images, batched_inputs, num_predictions, use_nms, nms_threshold, rle=False, device_masks=False, window=None,
-               owner=None, index_map=None):
+               owner=None, index_map=None, paint=None):
     """window = (W, O): a video of more than W frames runs window by window and is stitched (window_inference.run_windows); one of
-    at most W frames, or window = None, is the one-clip path.  owner.last_windows receives the number of windows run."""
+    at most W frames, or window = None, is the one-clip path.  owner.last_windows receives the number of windows run.  paint (the
+    inference_paint switch) is refused under a window: stitched windows are not painted."""
+    if paint is not None and window is not None:
+        raise ValueError("inference_paint does not run under TEST.WINDOW_INFERENCE: stage-1 frame masks are painted per clip "
+                         "(keymask.frame_masks --frames-per-call); turn the window off")
     video = batched_inputs[0]
     if owner is not None:
         owner.last_windows = 1
@@ -666,7 +672,7 @@ def _inference(net, images, batched_inputs, num_predictions, use_nms, nms_thresh
     height, width = video.get("height", image_size[0]), video.get("width", image_size[1])   # :351-352
     return inference_video(cls, ml, dims, tuple(images.shape[1:3]),
                            image_size, (int(height), int(width)), num_predictions, use_nms, nms_threshold, rle=rle,
-                           device_masks=device_masks, index_map=index_map)
+                           device_masks=device_masks, index_map=index_map, paint=paint)
 
 
 @META_ARCH_REGISTRY.register()
@@ -686,6 +692,7 @@ class VideoMaskFormer(nn.Module):
         self.inference_rle = False                  # see KDVideoMaskFormer
         self.inference_device_masks = False
         self.inference_index = None
+        self.inference_paint = None
         self.window_inference, self.window_size, self.window_overlap = bool(window_inference), int(window_size), int(window_overlap)
         self.last_windows = 0
 
@@ -775,7 +782,7 @@ class VideoMaskFormer(nn.Module):
                                   rle=getattr(self, "inference_rle", False),
                                   device_masks=getattr(self, "inference_device_masks", False),
                                   window=(self.window_size, self.window_overlap) if self.window_inference else None, owner=self,
-                                  index_map=getattr(self, "inference_index", None))
+                                  index_map=getattr(self, "inference_index", None), paint=getattr(self, "inference_paint", None))
         Hp, Wp = images.shape[1:3]
         gt = TargetSet.from_list(_gt_target_list(batched_inputs, self.num_frames, Hp, Wp, self.device), device=self.device)
         params = [p for p in list(self.backbone.parameters()) + list(self.sem_seg_head.parameters()) if p.requires_grad]

@@ -49,13 +49,11 @@ def index_map_options(index_map):
     return opts["rule"], int(opts["max_proposals"]), float(opts["score_threshold"])
 
 
-def _inference_index(class_logits, mask_logits, dims, padded, img_size, out_size, num_predictions, use_nms, nms_threshold, index_map):
-    """inference_video(index_map=...): the proposals are infer_select's top num_predictions, without those scored below the
+def _select_proposals(class_logits, mask_logits, dims, padded, img_size, out_size, num_predictions, use_nms, nms_threshold, threshold,
+                      max_proposals):
+    """the proposals of the plane-free outputs (index_map, paint): infer_select's top num_predictions, without those scored below the
     threshold, (use_nms) without those the greedy mask-NMS suppresses -- the only step that still needs bit planes, of the
-    thresholded candidates -- and of the rest the first max_proposals; label p + 1 of the map is pred_scores[p]"""
-    rule, max_proposals, threshold = index_map_options(index_map)
-    T = dims[0]
-    dev = mask_logits.device
+    thresholded candidates -- and of the rest the first max_proposals -> (scores, query, label) on the device, or None for none"""
     sel = []
     if class_logits.shape[0]:
         scores, query, label = ops.infer_select(class_logits, num_predictions)
@@ -66,18 +64,64 @@ def _inference_index(class_logits, mask_logits, dims, padded, img_size, out_size
             sel = greedy_mask_nms(ops.mask_pair_counts(bits).cpu().numpy(), label[:n].cpu().numpy(), nms_threshold)
         sel = sel[:max_proposals]
     if not sel:
-        index = torch.zeros((T,) + tuple(out_size), device=dev, dtype=torch.uint8)
+        return None
+    idx = torch.as_tensor(sel, device=mask_logits.device, dtype=torch.long)
+    return scores[idx].contiguous(), query[idx].contiguous(), label[idx]
+
+
+def _inference_index(class_logits, mask_logits, dims, padded, img_size, out_size, num_predictions, use_nms, nms_threshold, index_map):
+    """inference_video(index_map=...): the proposals of _select_proposals; label p + 1 of the map is pred_scores[p]"""
+    rule, max_proposals, threshold = index_map_options(index_map)
+    picked = _select_proposals(class_logits, mask_logits, dims, padded, img_size, out_size, num_predictions, use_nms, nms_threshold,
+                               threshold, max_proposals)
+    if picked is None:
+        index = torch.zeros((dims[0],) + tuple(out_size), device=mask_logits.device, dtype=torch.uint8)
         return {"image_size": tuple(out_size), "pred_scores": [], "pred_labels": [], "pred_masks": index, "pred_masks_format": "index_u8"}
-    idx = torch.as_tensor(sel, device=dev, dtype=torch.long)
-    scores, query, label = scores[idx].contiguous(), query[idx].contiguous(), label[idx]
+    scores, query, label = picked
     index = ops.infer_index(mask_logits, dims, padded, img_size, out_size, query, scores, rule)
     return {"image_size": tuple(out_size), "pred_scores": scores.tolist(), "pred_labels": label.tolist(), "pred_masks": index,
             "pred_masks_format": "index_u8"}
 
 
+def paint_options(paint):
+    """{"max_masks", "score_threshold", "colors"} with the defaults (50, 0.35, None: ops.mask_colors) filled in; unknown keys, mask
+    counts outside 1..254 and a colour table that is not u8 [>= max_masks, 3] are refused"""
+    opts = {"max_masks": 50, "score_threshold": 0.35, "colors": None}
+    unknown = set(paint) - set(opts)
+    if unknown:
+        raise ValueError(f"paint keys {sorted(unknown)}: max_masks, score_threshold and colors are known")
+    opts.update(paint)
+    max_masks = int(opts["max_masks"])
+    if not 1 <= max_masks <= ops.PAINT_MAX_PROPOSALS:
+        raise ValueError(f"paint max_masks = {opts['max_masks']}: 1..{ops.PAINT_MAX_PROPOSALS}")
+    colors = ops.mask_colors(max_masks) if opts["colors"] is None else np.asarray(opts["colors"])
+    if colors.dtype != np.uint8 or colors.ndim != 2 or colors.shape[1] != 3 or colors.shape[0] < max_masks:
+        raise ValueError(f"paint colors must be uint8 [>= {max_masks}, 3], got {colors.dtype} {colors.shape}")
+    return max_masks, float(opts["score_threshold"]), colors
+
+
+def _inference_paint(class_logits, mask_logits, dims, padded, img_size, out_size, num_predictions, use_nms, nms_threshold, paint):
+    """inference_video(paint=...): the proposals of _select_proposals painted by ops.paint_frames; colour p of the table and label
+    p + 1 of pred_index are pred_scores[p]"""
+    max_masks, threshold, colors = paint_options(paint)
+    dev = mask_logits.device
+    picked = _select_proposals(class_logits, mask_logits, dims, padded, img_size, out_size, num_predictions, use_nms, nms_threshold,
+                               threshold, max_masks)
+    if picked is None:
+        shape = (dims[0],) + tuple(out_size)
+        return {"image_size": tuple(out_size), "pred_scores": [], "pred_labels": [], "pred_areas": [],
+                "pred_masks": torch.zeros(shape + (3,), device=dev, dtype=torch.uint8),
+                "pred_index": torch.zeros(shape, device=dev, dtype=torch.uint8), "pred_masks_format": "rgb_u8"}
+    scores, query, label = picked
+    table = torch.from_numpy(np.ascontiguousarray(colors[:query.shape[0]])).to(dev)
+    rgb, index, areas, _ = ops.paint_frames(mask_logits, dims, padded, img_size, out_size, query, table)
+    return {"image_size": tuple(out_size), "pred_scores": scores.tolist(), "pred_labels": label.tolist(), "pred_areas": areas.tolist(),
+            "pred_masks": rgb, "pred_index": index, "pred_masks_format": "rgb_u8"}
+
+
 @torch.no_grad()
 def inference_video(class_logits, mask_logits, dims, padded, img_size, out_size, num_predictions, use_nms=False,
-                    nms_threshold=0.75, rle=False, device_masks=False, index_map=None):
+                    nms_threshold=0.75, rle=False, device_masks=False, index_map=None, paint=None):
     """class_logits [Q,C+1]; mask_logits pixel-major [T*hm*wm, ldq] of ONE video; dims = (T, hm, wm); padded = network
     input size (Hp,Wp), img_size = size without padding, out_size = (height, width) of the original video.
     Returns the reference's dict: image_size, pred_scores (list of float), pred_labels (list of int), pred_masks (list of
@@ -86,7 +130,16 @@ def inference_video(class_logits, mask_logits, dims, padded, img_size, out_size,
     device_masks=True: `pred_masks` is the CUDA u8 tensor [K,T,H,W] (0 / 1, after NMS) with "pred_masks_format": "device_u8".
     index_map={"rule": "rank" | "prob", "max_proposals": 20, "score_threshold": 0.0}: `pred_masks` is ONE CUDA u8 tensor [T,H,W]
     of non-overlapping proposal labels (0: none, p + 1: the proposal of pred_scores[p]; ops.infer_index), "pred_masks_format":
-    "index_u8"; not together with rle / device_masks."""
+    "index_u8"; not together with rle / device_masks.
+    paint={"max_masks": 50, "score_threshold": 0.35, "colors": None}: the stage-1 pseudo-mask picture (ops.paint_frames): `pred_masks`
+    is the CUDA u8 RGB tensor [T,H,W,3] ("pred_masks_format": "rgb_u8"), `pred_index` the u8 [T,H,W] owner map (p + 1: the proposal of
+    pred_scores[p]), `pred_areas` K lists of T pixel counts; not together with rle / device_masks / index_map."""
+    if paint is not None:
+        if rle or device_masks or index_map is not None:
+            raise ValueError("paint replaces pred_masks by one RGB picture per frame: it does not combine with rle / device_masks / "
+                             "index_map")
+        return _inference_paint(class_logits, mask_logits, dims, padded, img_size, out_size, num_predictions, use_nms, nms_threshold,
+                                paint)
     if index_map is not None:
         if rle or device_masks:
             raise ValueError("index_map replaces pred_masks by one label map: it does not combine with rle / device_masks")
