@@ -697,6 +697,53 @@ int s2d_mask_plane_bbox_ragged_u32(const uint32_t *bits, const long *plane, int 
 int s2d_selftrain_keep_ragged(const long long *inter, const int *area_d, const int *area_g, const long *img, int N, int *keep,
                               hipStream_t stream);
 
+/* s2d_mask_plane_areas_u32 for the chunk: area [P] = set bits of plane p (mask_util.area), the same device body; 0 for a row that
+ * does not fit the buffer.  One workgroup per plane.  Arguments as s2d_mask_plane_bbox_ragged_u32's. */
+int s2d_mask_plane_areas_ragged_u32(const uint32_t *bits, const long *plane, int P, long total_words, unsigned *area, hipStream_t stream);
+
+/* ---- Video self-training merge (s2d_amd/selftrain_video.py, csrc/selftrain_video.hip).  The rule is this project's own: the image
+ * merge above carried to tubes (whole tracks); the reference has no video merge.  Both calls handle a CHUNK of N videos of different
+ * sizes and lengths in one launch.
+ *
+ * Tube layout.  A track is its T frame planes back to back in the flat buffer of the ragged RLE decode (an absent frame is a plane
+ * with 0 runs: all zero), so a track of an H x W video of T frames is T * wpp words.  The P side of a video (the previous round's
+ * tracks) is its D tracks back to back, the Q side (the kept predictions) its G tracks.  P-side tracks of the chunk are numbered
+ * flat, video after video; so are the Q-side tracks.  The pairs of a video are a row-major [D][G] block; the blocks lie back to
+ * back in `inter` / `uni`.  videos is a DEVICE int64 table [N][11], one row per video:
+ *    0 p_word  first word of the video's D P-side tracks in `bits`      1 q_word  first word of its G Q-side tracks
+ *    2 wpp     words per plane, ceil(H*W / 32)                          3 hw      H*W (< 2^31)
+ *    4 T       frames per track                                         5 D       6 G
+ *    7 d0      flat number of the video's first P-side track            8 g0      of its first Q-side track
+ *    9 pair0   offset of its [D][G] block in `inter` / `uni`           10 pres0   offset of its [D][T] block in `present`
+ * present is a DEVICE uint8 array [n_present], n_present = sum of D*T: present[pres0 + d*T + t] != 0 where frame t is in the frame
+ * set of P-side track d of the video (all ones when every frame counts).  A row that does not fit the buffers it names (negative
+ * entries, wpp != ceil(hw/32), track words outside [0, total_words), present or pair block outside its array) is skipped by the
+ * kernels: nothing is read or written for it. ------------------------------------------------------------------------------- */
+
+/* Tube counts of every (P-side track d, Q-side track g) pair of the chunk, as unsigned 64-bit integers:
+ *   inter[pair] = sum over the frames t of d's frame set of |d_t & g_t|
+ *   uni[pair]   = sum over the same frames of |d_t| + |g_t| - |d_t & g_t|
+ * A frame outside d's frame set adds nothing to either count of d's pairs.  Bits of a plane's last word at and beyond H*W are not
+ * counted.  tiles: DEVICE int32 [n_tiles][3] = {video, ti, tj}: the 8 x 8 pair tile (P-side tracks 8*ti.., Q-side tracks 8*tj..); the
+ * host lists ceil(D/8) * ceil(G/8) tiles for every video with D > 0 and G > 0, each exactly once.  max_track_words: the largest
+ * T * wpp of the chunk (< 2^40); it only sizes the grid: the frame-words of a tile are split over workgroups whose partial sums are
+ * added with integer atomics (a video whose T * wpp exceeds it is skipped).  accumulate == 0: inter and uni (n_pairs elements each)
+ * are zeroed by the call; != 0: the call adds to what they hold, so a long video may be counted in slabs of frames, each slab its
+ * own buffer, tables and call.  Exact integers, no float anywhere: the result does not depend on the order of the atomics and a
+ * second call is bitwise equal.  The call only enqueues.  N == 0 or n_pairs == 0 is a no-op that returns S2D_OK; a negative count or
+ * a null pointer returns S2D_ERR_ARG with nothing launched and nothing written (tiles may be null when n_tiles == 0). */
+int s2d_tube_counts_ragged(const uint32_t *bits, long total_words, const long *videos, int N, const uint8_t *present, long n_present,
+                           const int *tiles, int n_tiles, long max_track_words, unsigned long long *inter, unsigned long long *uni,
+                           long n_pairs, int accumulate, hipStream_t stream);
+
+/* The keep rule on the tube counts (same videos table; columns 5, 6, 7, 9 are read): keep[d] (int32 [n_keep], flat P-side numbering)
+ * = 1 iff EVERY g of the same video has 2 * inter < uni (int64), so 1 for a video with G == 0.  A pair with uni == 0 (a track
+ * with no frame in its frame set, or empty masks on both sides) fails the test, as in s2d_selftrain_keep_ragged.  inter / uni may
+ * be null when n_pairs == 0, keep when n_keep == 0.  N == 0 is a no-op that returns S2D_OK; a negative count or another null
+ * pointer returns S2D_ERR_ARG with nothing launched. */
+int s2d_selftrain_keep_tube_ragged(const unsigned long long *inter, const unsigned long long *uni, long n_pairs, const long *videos, int N,
+                                   int *keep, long n_keep, hipStream_t stream);
+
 /* ---- test-time frame resize (s2d_amd/data/resize.py, data/test_loader.py): detectron2 ResizeTransform.apply_image =
  * PIL Image.resize(BILINEAR) on uint8 RGB frames, bit-exact ------------------------------------------------------------- */
 

@@ -1,5 +1,6 @@
-// Device and host pieces shared by the kernels that work on packed bit planes: mask_counts.hip and coco_eval.hip (pair popcounts),
-// mask_boundary.hip and davis_eval.hip (morphology on rows that are not word-aligned).
+// Device and host pieces shared by the kernels that work on packed bit planes: mask_counts.hip, coco_eval.hip and
+// selftrain_video.hip (pair popcounts), mask_counts.hip and rle_ragged.hip (plane areas), mask_boundary.hip and davis_eval.hip
+// (morphology on rows that are not word-aligned).
 //
 // THE PLANE LAYOUT.  A plane of H x W pixels is FLAT: pixel i = y * W + x -> word i / 32, bit i % 32, ceil(H * W / 32) words (what
 // s2d_pack_mask_bits_u8 and s2d_rle_decode_bits write), so rows are not word-aligned unless W % 32 == 0.  The padding bits of a
@@ -49,6 +50,20 @@ template <int N> struct PopcTile {
         return x < N * N ? (unsigned long long)red[0][x] + red[1][x] + red[2][x] + red[3][x] : 0ull;
     }
 };
+
+// area[0] = the set bits of the wpf words of plane pl (mask_util.area), for the fixed-size and the ragged entry point alike.  All
+// 256 threads of the workgroup call this (it holds a barrier).
+__device__ __forceinline__ void plane_popcount(const uint32_t *__restrict__ pl, long wpf, unsigned int *__restrict__ area)
+{
+    __shared__ unsigned int red[4];
+    unsigned int s = 0;
+    for (long w = threadIdx.x; w < wpf; w += 256) s += __popc(pl[w]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) area[0] = red[0] + red[1] + red[2] + red[3];
+}
 
 // Chunks of the word range for a launch of `tiles` tile workgroups per chunk that add their partial sums with atomics.
 static inline int popc_chunks(long words, long tiles)

@@ -13,15 +13,7 @@ namespace {
 
 __global__ __launch_bounds__(256) void plane_popcount_kernel(const uint32_t *__restrict__ bits, long wpf, unsigned int *__restrict__ area)
 {
-    __shared__ unsigned int red[4];
-    const uint32_t *pl = bits + (long)blockIdx.x * wpf;
-    unsigned int s = 0;
-    for (long w = threadIdx.x; w < wpf; w += 256) s += __popc(pl[w]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) area[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    plane_popcount(bits + (long)blockIdx.x * wpf, wpf, area + blockIdx.x);
 }
 
 constexpr int PT = 8;

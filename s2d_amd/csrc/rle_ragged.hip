@@ -1,4 +1,4 @@
-// RLE parse, decode and tight boxes for a CHUNK of planes of different sizes, one launch each however many images the chunk holds
+// RLE parse, decode, tight boxes and areas for a CHUNK of planes of different sizes, one launch each however many images the chunk holds
 // (s2d_amd/rle_ragged.py), and the keep rule of the image self-training merge (s2d_amd/selftrain.py; the reference's
 // model_training/cutler/tools/get_self_training_ann.py:161-166).  The per-plane bodies are those of the fixed-size entry points
 // (rle_planes.h; ytvis_eval.hip): here H, W and the word base of a plane come from its row of the plane table
@@ -8,6 +8,7 @@
 // which is the COCO chunk layout (include/s2d_hip.h, "Ragged layout"), so s2d_coco_mask_iou_ragged reads the decoded buffer in place.
 // A row the buffer cannot hold (H or W < 1, H*W >= 2^31, words outside [0, total_words)) is skipped by every kernel: nothing is read
 // or written for it.  The host checks the table before the call; the kernels do not rely on that.
+#include "bitplane.h"
 #include "rle_planes.h"
 
 namespace {
@@ -76,6 +77,18 @@ __global__ __launch_bounds__(256) void plane_bbox_ragged_kernel(const uint32_t *
     plane_tight_box(bits + q.word0, q.H, q.W, q.wpp, b);
 }
 
+// plane_popcount_kernel (mask_counts.hip) with the plane taken from its table row: the same body, a skipped row has area 0
+__global__ __launch_bounds__(256) void plane_areas_ragged_kernel(const uint32_t *__restrict__ bits, const long *__restrict__ plane,
+                                                                 long total_words, unsigned int *__restrict__ area)
+{
+    const PlaneRow q = plane_row(plane, blockIdx.x, total_words);     // uniform over the workgroup
+    if (!q.ok) {
+        if (threadIdx.x == 0) area[blockIdx.x] = 0u;
+        return;
+    }
+    plane_popcount(bits + q.word0, q.wpp, area + blockIdx.x);
+}
+
 constexpr int KEEP_T = 64;
 
 // one workgroup (a wave) per image, a thread per previous-round mask d: keep[dt0 + d] = every g has 2 * inter < union
@@ -132,6 +145,16 @@ int s2d_mask_plane_bbox_ragged_u32(const uint32_t *bits, const long *plane, int 
     if (P == 0) return S2D_OK;
     if (!bits || !plane || !bbox) return S2D_ERR_ARG;
     hipLaunchKernelGGL(plane_bbox_ragged_kernel, dim3(P), dim3(256), 0, stream, bits, plane, total_words, bbox);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_mask_plane_areas_ragged_u32(const uint32_t *bits, const long *plane, int P, long total_words, unsigned *area, hipStream_t stream)
+{
+    if (P < 0 || total_words < 0) return S2D_ERR_ARG;
+    if (P == 0) return S2D_OK;
+    if (!bits || !plane || !area) return S2D_ERR_ARG;
+    hipLaunchKernelGGL(plane_areas_ragged_kernel, dim3(P), dim3(256), 0, stream, bits, plane, total_words, area);
     S2D_CHECK_LAUNCH();
     return S2D_OK;
 }
