@@ -1133,6 +1133,34 @@ int s2d_window_pair_counts(const float *A, const float *B, long n, int ldq, int 
 int s2d_window_scatter_columns(const float *src, long rows, int ldq, int Q, const int *perm, float *dst, long row0,
                                hipStream_t stream);
 
+/* ---- connected components of index maps (s2d_amd/index_components.py) --------------------------------------- */
+
+/* index u8 [N][H][W] is a map as s2d_infer_paint_u8 / s2d_infer_index_u8 write it: 0 = background, any other byte (255 included) an
+ * instance id.  A component is a maximal set of pixels of ONE non-zero id connected under conn = 4 or 8; pixels of different ids
+ * never join and background is not labelled.  All ids of a frame in one pass, no plane per id.
+ * s2d_index_components_tile: the tile (th rows x tw columns) a workgroup labels locally before the tiles are merged.
+ * s2d_index_components_workspace_bytes: the scratch both calls below need for [N][H][W] (any address; the calls align it themselves);
+ * S2D_ERR_ARG for N, H or W < 1 or H*W >= 2^31 - 1.
+ * s2d_index_components_i32: labels i32 [N][H][W] = 0 on background, else 1 + (y*W + x) of the component's first pixel in raster
+ * order -- a name that depends on nothing but the map, so a second call is bitwise equal and any host labelling compares by
+ * equality.  area i32 [N][H][W] (may be NULL): area[n][p] = pixels of the component whose first pixel is p, 0 everywhere else.
+ * Three launches (tile-local union-find in LDS; lock-free merge across tile borders through agent-scope atomics; flatten, with one
+ * integer atomic per tile-local component for the areas), none of which waits for another workgroup.
+ * s2d_index_filter_components_u8 (labels, area: what the call above wrote for index): a component is kept iff area >= min_area and,
+ * with keep_largest != 0, it is the largest component of its (image, id), among equal areas the one with the lowest first pixel.
+ * out u8 [N][H][W] = index where the pixel's component is kept, else 0; out may be index.  rgb u8 [N][H][W][3] (may be NULL) is
+ * changed in place: the three bytes of every removed pixel become 0 and no other byte is touched.  removed i32 [N] = pixels removed
+ * per image (zeroed by the call, like the [N][256] table of largest components in the workspace).
+ * Any H, W >= 1 and any alignment of the byte arrays and of the workspace; the i32 arrays are 4-byte aligned.  conn other than 4 or
+ * 8, N, H or W < 1, H*W >= 2^31 - 1, min_area < 0, a NULL pointer other than area (components) or rgb (filter) or a misaligned i32
+ * array return S2D_ERR_ARG before anything is launched. */
+int s2d_index_components_tile(int *th, int *tw);
+long s2d_index_components_workspace_bytes(int N, int H, int W);
+int s2d_index_components_i32(const uint8_t *index, int N, int H, int W, int conn, int *labels, int *area, void *workspace,
+                             hipStream_t stream);
+int s2d_index_filter_components_u8(const uint8_t *index, const int *labels, const int *area, int N, int H, int W, int min_area,
+                                   int keep_largest, uint8_t *out, uint8_t *rgb, int *removed, void *workspace, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,11 @@ per frame on the device (ops.infer_index; --index-rule rank: a pixel goes to its
 score * sigmoid(logit)), which davis_eval.DAVISEvaluator scores where it is (--bound-th: the F-measure's boundary tolerance) and
 writes as OUT/davis/<sequence>/<frame>.png.  OUT/global_results.csv, OUT/per-sequence_results.csv, OUT/metrics.json =
 {"davis": {...}}; the timing line counts `videos`.  --boundary-ap and --iou-types are refused.  Parity with the DAVIS toolkit is
-unpinned (davis_eval.py)."""
+unpinned (davis_eval.py).  --min-component-area N (default 0), --keep-largest and --component-connectivity {4,8} (default 8) clean
+every map on the device before it is scored and written (ops.filter_components: of a proposal's pixels in a frame, connected
+components smaller than N pixels become background, and with --keep-largest every component but its largest); the timing line then
+counts `removed_pixels`.  They are DAVIS options: any other --test-format refuses them by name.  With the defaults no component
+kernel is launched."""
 import argparse
 import json
 import os
@@ -63,6 +67,12 @@ def parse_args(argv=None):
     ap.add_argument("--max-proposals", type=int, default=20, help="davis: proposals per sequence (<= 254)")
     ap.add_argument("--score-threshold", type=float, default=0.0, help="davis: proposals scored below it are dropped")
     ap.add_argument("--bound-th", type=float, default=0.008, help="davis: boundary tolerance of the F-measure")
+    ap.add_argument("--min-component-area", type=int, default=0, help="davis: connected components of a proposal smaller than this "
+                                                                      "become background (0: off)")
+    ap.add_argument("--keep-largest", action="store_true", help="davis: keep only the largest connected component of every proposal "
+                                                                "per frame")
+    ap.add_argument("--component-connectivity", type=int, choices=(4, 8), default=None, help="davis: pixel connectivity of the "
+                                                                                             "components (default 8)")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="config overrides KEY VALUE ...")
     return ap.parse_args(argv)
 
@@ -126,6 +136,20 @@ def resolve_test_format(fmt, doc, boundary=False, iou_types=None):
     return fmt
 
 
+def component_arguments(a, fmt):
+    """the component cleanup options of the parsed command line -> the keys they add to the `davis` dict; with any format but davis
+    an option that was given is refused by name"""
+    given = [name for name, on in (("--min-component-area", a.min_component_area != 0), ("--keep-largest", a.keep_largest),
+                                   ("--component-connectivity", a.component_connectivity is not None)) if on]
+    if fmt != "davis":
+        if given:
+            raise ValueError(f"{', '.join(given)} clean{'s' if len(given) == 1 else ''} DAVIS index maps: not available with "
+                             f"--test-format {fmt}")
+        return {}
+    return {"min_component_area": a.min_component_area, "keep_largest": a.keep_largest,
+            "component_connectivity": 8 if a.component_connectivity is None else a.component_connectivity}
+
+
 def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, prefetch=2, boundary=False, dilation_ratio=0.02,
                    test_format="ytvis", iou_types=None, davis=None):
     """score `model` on a YTVIS split: every video through `model([inputs])` (eval mode, predictions as COCO RLE) with the test
@@ -136,7 +160,9 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
     iou_types (image format only; None: ("segm", "bbox")) chooses those dicts, "boundary" among them.
     A directory as `gt` (test_format "davis" or "auto"): a DAVIS tree -- davis_video_document, the model's inference_index switch and
     DAVISEvaluator; `davis` = {"sequences", "rule", "max_proposals", "score_threshold", "bound_th"} (defaults: every sequence, "rank",
-    20, 0.0, 0.008); files output_dir/davis/<sequence>/<frame>.png, the two CSVs and metrics.json = {"davis": the global table}.
+    20, 0.0, 0.008) and the cleanup keys "min_component_area", "keep_largest", "component_connectivity" (0, False, 8:
+    postprocess.index_map_options; the cleaned maps are the ones scored and written, the timing line gains `removed_pixels`); files
+    output_dir/davis/<sequence>/<frame>.png, the two CSVs and metrics.json = {"davis": the global table}.
     The model's training mode and inference switches are restored afterwards.  -> (results, timing line dict)"""
     from .data.test_loader import YTVISTestLoader
     from .ytvis_eval import YTVISEvaluator
@@ -147,9 +173,12 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
     index_map = None
     if is_davis:
         from .data.davis_loader import davis_video_document
-        opt = {"sequences": None, "rule": "rank", "max_proposals": 20, "score_threshold": 0.0, "bound_th": 0.008, **(davis or {})}
+        opt = {"sequences": None, "rule": "rank", "max_proposals": 20, "score_threshold": 0.0, "bound_th": 0.008,
+               "min_component_area": 0, "keep_largest": False, "component_connectivity": 8, **(davis or {})}
         gt_dir, gt = gt, davis_video_document(image_root, gt, opt["sequences"])     # refuses a broken tree before the model runs
-        index_map = {"rule": opt["rule"], "max_proposals": opt["max_proposals"], "score_threshold": opt["score_threshold"]}
+        index_map = {"rule": opt["rule"], "max_proposals": opt["max_proposals"], "score_threshold": opt["score_threshold"],
+                     "min_component_area": opt["min_component_area"], "keep_largest": opt["keep_largest"],
+                     "component_connectivity": opt["component_connectivity"]}
     elif test_format == "davis":
         resolve_test_format(test_format, gt, boundary, iou_types)                    # raises: not a directory
     if isinstance(gt, str):
@@ -184,6 +213,7 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
     model.inference_rle = not is_davis
     model.inference_index = index_map
     nvid = nfr = nwin = 0
+    removed = []                                                      # device counts of the component cleanup: read after the loop
     try:
         torch.cuda.synchronize(device)
         t0 = time.perf_counter()
@@ -191,6 +221,8 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
             for inputs in loader:
                 outputs = model([inputs])
                 evaluator.process([inputs], outputs)
+                if "pred_removed" in outputs:
+                    removed.append(outputs["pred_removed"])
                 nvid += 1
                 nfr += len(inputs["image"])
                 nwin += getattr(model, "last_windows", 1)
@@ -217,6 +249,8 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
             "images_per_s" if images else "videos_per_s": round(nvid / wall, 4) if wall > 0 else None,
             "frames_per_s": round(nfr / wall, 3) if wall > 0 else None,
             "loader_wait_fraction": round(loader.wait_s / wall, 4) if wall > 0 else None}
+    if is_davis and (opt["min_component_area"] > 0 or opt["keep_largest"]):
+        line["removed_pixels"] = sum(int(r.sum()) for r in removed)
     return results, line
 
 
@@ -242,10 +276,12 @@ def main(argv=None):
         with open(a.gt) as fh:
             gt_doc = json.load(fh)
     fmt = resolve_test_format(a.test_format, gt_doc, a.boundary_ap, iou_types)
+    cleanup = component_arguments(a, fmt)
     if fmt == "davis":                                                  # a broken tree is refused before the model is built
         from .data.davis_loader import davis_video_document
         from .modeling.postprocess import index_map_options
-        index_map_options({"rule": a.index_rule, "max_proposals": a.max_proposals, "score_threshold": a.score_threshold})
+        index_map_options({"rule": a.index_rule, "max_proposals": a.max_proposals, "score_threshold": a.score_threshold, **cleanup})
+        davis.update(cleanup)
         davis_video_document(a.image_root, a.gt, a.sequences)
     model = build_model(cfg, a.weights or cfg.MODEL.WEIGHTS, device)
     results, line = evaluate_model(cfg, model, gt_doc, a.image_root, a.output_dir, device, a.threads, a.prefetch,

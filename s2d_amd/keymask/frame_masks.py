@@ -3,7 +3,8 @@
     python -m s2d_amd.keymask.frame_masks --config-file X.yaml --weights W.pth \\
         --video-base-path D/DAVIS/JPEGImages/480p --mask-base-path M \\
         [--confidence-threshold 0.35] [--max-masks 50] [--frames-per-call 1] [--job-id J --videos-per-job N] [--overwrite]
-        [--threads 8] [--prefetch 2] [--dataset-name NAME] [KEY VALUE ...]
+        [--threads 8] [--prefetch 2] [--dataset-name NAME]
+        [--min-component-area N] [--keep-largest] [--component-connectivity {4,8}] [KEY VALUE ...]
 
 Restates what model_training/cutler/demo/demo.py does with its image model for this project's own checkpoint (one trained on image
 annotations as pseudo-clips, `train --train-format coco_image`, or any other): the instances scored at least
@@ -23,9 +24,17 @@ Where this differs from the reference, on purpose: the colours are the project's
 entries 1..n) and not detectron2's; equal areas are painted in proposal order (a stable sort) where numpy's argsort leaves the
 order open; more instances than colours are cut to the first --max-masks instead of an IndexError past 50; --frames-per-call.
 
+--min-component-area N (default 0), --keep-largest and --component-connectivity {4,8} (default 8) clean the painted owner map before
+the PNGs are written (ops.filter_components, s2d_amd/index_components.py): of every instance's pixels in a frame, a connected
+component smaller than N pixels is removed, and with --keep-largest every component but the instance's largest in that frame (equal
+areas: the one whose first pixel comes first in raster order).  A removed pixel becomes black even where a larger instance painted
+underneath also holds it: the plane-free paint keeps no second owner.  With the defaults no component kernel is launched and every
+output byte is as before.
+
 The run ends with one JSON line on stdout: videos (folders of this job), skipped, frames (written), masks (proposals with a
-non-zero area, summed over frames), empty_frames (frames in which none has one), wall_s, frames_per_s, loader_wait_fraction,
-encode_s (seconds inside PNG encoding, summed over the pool's threads)."""
+non-zero area, summed over frames), empty_frames (frames in which none has one), removed_pixels (pixels the component cleanup
+blackened; 0 with it off), wall_s, frames_per_s, loader_wait_fraction, encode_s (seconds inside PNG encoding, summed over the pool's
+threads)."""
 import argparse
 import json
 import os
@@ -55,6 +64,10 @@ def parse_args(argv=None):
     ap.add_argument("--prefetch", type=int, default=2)
     ap.add_argument("--dataset-name", default=None, help="frame-order rule of discover.make_paths instead of the one detected in "
                                                          "--video-base-path (no dataset in the path: numeric stems, as DAVIS)")
+    ap.add_argument("--min-component-area", type=int, default=0, help="connected components of an instance smaller than this are "
+                                                                      "blackened (0: off)")
+    ap.add_argument("--keep-largest", action="store_true", help="keep only the largest connected component of every instance per frame")
+    ap.add_argument("--component-connectivity", type=int, choices=(4, 8), default=8, help="pixel connectivity of the components")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="config overrides KEY VALUE ...")
     return ap.parse_args(argv)
 
@@ -155,14 +168,16 @@ class _Writer:
 
 
 def write_masks(cfg, model, video_base_path, mask_base_path, confidence_threshold=0.35, max_masks=50, frames_per_call=1, job_id=0,
-                videos_per_job=-1, overwrite=False, threads=8, prefetch=2, dataset_name=None, device=None):
+                videos_per_job=-1, overwrite=False, threads=8, prefetch=2, dataset_name=None, device=None, min_component_area=0,
+                keep_largest=False, component_connectivity=8):
     """every clip of folder_document through `model([inputs])` (eval mode, inference_paint) and its pictures to
     mask_base_path/<video>/<frame stem>.png -> the report dict of the module docstring.  The model's training mode and inference
     switches are restored afterwards."""
     import torch
     from ..data.test_loader import YTVISTestLoader
     from ..modeling.postprocess import paint_options
-    paint = {"max_masks": int(max_masks), "score_threshold": float(confidence_threshold)}
+    paint = {"max_masks": int(max_masks), "score_threshold": float(confidence_threshold), "min_component_area": min_component_area,
+             "keep_largest": keep_largest, "component_connectivity": component_connectivity}
     paint_options(paint)                                              # refused before anything is listed or run
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     doc, clips, counts = folder_document(video_base_path, mask_base_path, frames_per_call, job_id, videos_per_job, dataset_name,
@@ -173,6 +188,7 @@ def write_masks(cfg, model, video_base_path, mask_base_path, confidence_threshol
     model.eval()
     model.inference_rle, model.inference_device_masks, model.inference_index, model.inference_paint = False, False, None, paint
     frames = masks = empty = 0
+    removed = []                                                      # device counts: read once, after the last clip
     writer = _Writer(threads)
     try:
         torch.cuda.synchronize(device)
@@ -183,6 +199,8 @@ def write_masks(cfg, model, video_base_path, mask_base_path, confidence_threshol
                     out = model([inputs])
                     mdir, names = clips[inputs["video_id"]]
                     writer.submit(out["pred_masks"], mdir, names)
+                    if "pred_removed" in out:
+                        removed.append(out["pred_removed"])
                     T = len(names)
                     per_frame = [sum(1 for a in out["pred_areas"] if a[t] > 0) for t in range(T)]
                     frames += T
@@ -196,7 +214,8 @@ def write_masks(cfg, model, video_base_path, mask_base_path, confidence_threshol
         model.train(was_training)
         for s, v in was.items():
             setattr(model, s, v)
-    return {**counts, "frames": frames, "masks": masks, "empty_frames": empty, "wall_s": round(wall, 4),
+    return {**counts, "frames": frames, "masks": masks, "empty_frames": empty,
+            "removed_pixels": sum(int(r.sum()) for r in removed), "wall_s": round(wall, 4),
             "frames_per_s": round(frames / wall, 3) if wall > 0 else None,
             "loader_wait_fraction": round(loader.wait_s / wall, 4) if wall > 0 else None, "encode_s": round(writer.encode_s, 4)}
 
@@ -207,12 +226,14 @@ def main(argv=None):
     from ..config import load_config
     from ..evaluate import build_model
     from ..modeling.postprocess import paint_options
-    paint_options({"max_masks": a.max_masks, "score_threshold": a.confidence_threshold})
+    paint_options({"max_masks": a.max_masks, "score_threshold": a.confidence_threshold, "min_component_area": a.min_component_area,
+                   "keep_largest": a.keep_largest, "component_connectivity": a.component_connectivity})
     cfg = load_config(a.config_file, a.opts)
     device = torch.device("cuda", torch.cuda.current_device())
     model = build_model(cfg, a.weights or cfg.MODEL.WEIGHTS, device)
     line = write_masks(cfg, model, a.video_base_path, a.mask_base_path, a.confidence_threshold, a.max_masks, a.frames_per_call,
-                       a.job_id, a.videos_per_job, a.overwrite, a.threads, a.prefetch, a.dataset_name, device)
+                       a.job_id, a.videos_per_job, a.overwrite, a.threads, a.prefetch, a.dataset_name, device, a.min_component_area,
+                       a.keep_largest, a.component_connectivity)
     print(json.dumps(line), flush=True)
     return line
 

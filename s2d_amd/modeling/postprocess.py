@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..index_components import COMPONENT_KEYS
 
 
 def greedy_mask_nms(inter, labels, thr):
@@ -36,11 +37,14 @@ def greedy_mask_nms(inter, labels, thr):
 
 def index_map_options(index_map):
     """{"rule", "max_proposals", "score_threshold"} with the defaults ("rank", 20, 0.0) filled in; unknown keys, rules and proposal
-    counts outside 1..254 are refused"""
+    counts outside 1..254 are refused.  The component cleanup keys (ops.component_options: min_component_area, keep_largest,
+    component_connectivity) are known too and checked here; they are no part of the returned tuple."""
     opts = {"rule": "rank", "max_proposals": 20, "score_threshold": 0.0}
-    unknown = set(index_map) - set(opts)
+    unknown = set(index_map) - set(opts) - set(COMPONENT_KEYS)
     if unknown:
-        raise ValueError(f"index_map keys {sorted(unknown)}: rule, max_proposals and score_threshold are known")
+        raise ValueError(f"index_map keys {sorted(unknown)}: rule, max_proposals, score_threshold and {', '.join(COMPONENT_KEYS)} "
+                         "are known")
+    ops.component_options(index_map)
     opts.update(index_map)
     if opts["rule"] not in ops.INDEX_RULES:
         raise ValueError(f"index_map rule {opts['rule']!r}: one of {', '.join(ops.INDEX_RULES)}")
@@ -79,17 +83,25 @@ def _inference_index(class_logits, mask_logits, dims, padded, img_size, out_size
         return {"image_size": tuple(out_size), "pred_scores": [], "pred_labels": [], "pred_masks": index, "pred_masks_format": "index_u8"}
     scores, query, label = picked
     index = ops.infer_index(mask_logits, dims, padded, img_size, out_size, query, scores, rule)
-    return {"image_size": tuple(out_size), "pred_scores": scores.tolist(), "pred_labels": label.tolist(), "pred_masks": index,
-            "pred_masks_format": "index_u8"}
+    out = {"image_size": tuple(out_size), "pred_scores": scores.tolist(), "pred_labels": label.tolist(), "pred_masks": index,
+           "pred_masks_format": "index_u8"}
+    min_area, largest, conn = ops.component_options(index_map)
+    if min_area > 0 or largest:                                      # off: nothing is launched and no key is added
+        _, removed = ops.filter_components(index, min_area, largest, conn, out=index)
+        out["pred_removed"] = removed
+    return out
 
 
 def paint_options(paint):
     """{"max_masks", "score_threshold", "colors"} with the defaults (50, 0.35, None: ops.mask_colors) filled in; unknown keys, mask
-    counts outside 1..254 and a colour table that is not u8 [>= max_masks, 3] are refused"""
+    counts outside 1..254 and a colour table that is not u8 [>= max_masks, 3] are refused.  The component cleanup keys
+    (ops.component_options: min_component_area, keep_largest, component_connectivity) are known too and checked here; they are no
+    part of the returned tuple."""
     opts = {"max_masks": 50, "score_threshold": 0.35, "colors": None}
-    unknown = set(paint) - set(opts)
+    unknown = set(paint) - set(opts) - set(COMPONENT_KEYS)
     if unknown:
-        raise ValueError(f"paint keys {sorted(unknown)}: max_masks, score_threshold and colors are known")
+        raise ValueError(f"paint keys {sorted(unknown)}: max_masks, score_threshold, colors and {', '.join(COMPONENT_KEYS)} are known")
+    ops.component_options(paint)
     opts.update(paint)
     max_masks = int(opts["max_masks"])
     if not 1 <= max_masks <= ops.PAINT_MAX_PROPOSALS:
@@ -115,8 +127,15 @@ def _inference_paint(class_logits, mask_logits, dims, padded, img_size, out_size
     scores, query, label = picked
     table = torch.from_numpy(np.ascontiguousarray(colors[:query.shape[0]])).to(dev)
     rgb, index, areas, _ = ops.paint_frames(mask_logits, dims, padded, img_size, out_size, query, table)
-    return {"image_size": tuple(out_size), "pred_scores": scores.tolist(), "pred_labels": label.tolist(), "pred_areas": areas.tolist(),
-            "pred_masks": rgb, "pred_index": index, "pred_masks_format": "rgb_u8"}
+    out = {"image_size": tuple(out_size), "pred_scores": scores.tolist(), "pred_labels": label.tolist(), "pred_areas": areas.tolist(),
+           "pred_masks": rgb, "pred_index": index, "pred_masks_format": "rgb_u8"}
+    min_area, largest, conn = ops.component_options(paint)
+    if min_area > 0 or largest:                                      # off: nothing is launched and no key is added
+        # a removed pixel becomes black even where a larger instance painted underneath also holds it: the paint keeps no second
+        # owner.  pred_areas stay the areas the draw order was decided by
+        _, removed = ops.filter_components(index, min_area, largest, conn, rgb=rgb, out=index)
+        out["pred_removed"] = removed
+    return out
 
 
 @torch.no_grad()
@@ -133,7 +152,10 @@ def inference_video(class_logits, mask_logits, dims, padded, img_size, out_size,
     "index_u8"; not together with rle / device_masks.
     paint={"max_masks": 50, "score_threshold": 0.35, "colors": None}: the stage-1 pseudo-mask picture (ops.paint_frames): `pred_masks`
     is the CUDA u8 RGB tensor [T,H,W,3] ("pred_masks_format": "rgb_u8"), `pred_index` the u8 [T,H,W] owner map (p + 1: the proposal of
-    pred_scores[p]), `pred_areas` K lists of T pixel counts; not together with rle / device_masks / index_map."""
+    pred_scores[p]), `pred_areas` K lists of T pixel counts; not together with rle / device_masks / index_map.
+    Both dicts also take "min_component_area": 0, "keep_largest": False, "component_connectivity": 8 (ops.filter_components): with an
+    area above 0 or keep_largest the map is cleaned in place -- in the picture the removed pixels become black -- and `pred_removed`
+    is the CUDA int32 [T] count of removed pixels per frame; with the defaults nothing is launched and the key is absent."""
     if paint is not None:
         if rle or device_masks or index_map is not None:
             raise ValueError("paint replaces pred_masks by one RGB picture per frame: it does not combine with rle / device_masks / "

@@ -760,6 +760,8 @@ def infer_masks(mask_logits, dims, padded, img_size, out_size, query, want_bits=
 from .index_map import INDEX_MAX_PROPOSALS, INDEX_RULES, infer_index  # noqa: E402,F401
 # stage-1 frame masks (s2d_infer_frame_areas_i32, s2d_infer_paint_u8): defined in frame_paint.py, re-exported the same way
 from .frame_paint import PAINT_MAX_PROPOSALS, infer_frame_areas, infer_paint, mask_colors, paint_frames  # noqa: E402,F401
+# connected components of those maps (s2d_index_components_i32, s2d_index_filter_components_u8): defined in index_components.py
+from .index_components import component_options, component_tile, filter_components, index_components  # noqa: E402,F401
 
 
 def pack_mask_bits(masks):
