@@ -701,6 +701,26 @@ int s2d_selftrain_keep_ragged(const long long *inter, const int *area_d, const i
  * does not fit the buffer.  One workgroup per plane.  Arguments as s2d_mask_plane_bbox_ragged_u32's. */
 int s2d_mask_plane_areas_ragged_u32(const uint32_t *bits, const long *plane, int P, long total_words, unsigned *area, hipStream_t stream);
 
+/* The way back: bit planes of the chunk -> COCO RLE strings, the dual of the three calls above and the ragged form of
+ * s2d_rle_count_u8 / s2d_rle_positions_u8 / s2d_rle_strings_u8, whose device bodies they run (csrc/rle_encode.h): the string of a
+ * plane is byte for byte the string of the same byte mask.  They work on a SELECTION of planes, sel DEVICE int32 [S] (any order,
+ * repeats allowed): only the planes a cleanup changed are encoded again.  col0 DEVICE int64 [S] = the widths W of the selection
+ * before entry s, summed (the host knows them); col_off int32 [sum of W] is scratch between the first two calls.
+ * s2d_rle_count_ragged_u32: nbound [S] = run boundaries of plane sel[s], area [S] its set pixels, bbox [S][4] = x, y, w, h (the tight
+ * box, zeros for an empty plane).  s2d_rle_positions_ragged_u32: positions[frame_off[s] + j] = the column-major position of boundary
+ * j; frame_off DEVICE int64 [S+1] = the exclusive scan of nbound.  s2d_rle_strings_ragged: as s2d_rle_strings_u8 with F = S and the
+ * last run of entry s closed at its own H*W; ncounts = frame_off[S] + S; chars [7 * ncounts], str_off DEVICE int64 [S+1]; workspace
+ * of s2d_rle_strings_ragged_workspace_bytes(ncounts) bytes.  Two read-backs per chunk: the boundary counts, then the strings.
+ * An entry of sel that names no plane the buffer holds has no boundaries, area 0 and a zero box.  S == 0 is a no-op; a negative
+ * count or a null pointer returns S2D_ERR_ARG with nothing launched. */
+int s2d_rle_count_ragged_u32(const uint32_t *bits, const long *plane, int P, long total_words, const int *sel, int S,
+                             const long *col0, int *col_off, int *nbound, int *area, int *bbox, hipStream_t stream);
+int s2d_rle_positions_ragged_u32(const uint32_t *bits, const long *plane, int P, long total_words, const int *sel, int S,
+                                 const long *col0, const int *col_off, const long *frame_off, int *positions, hipStream_t stream);
+long s2d_rle_strings_ragged_workspace_bytes(long ncounts);
+int s2d_rle_strings_ragged(const int *positions, const long *frame_off, const long *plane, int P, const int *sel, int S,
+                           long ncounts, void *workspace, long workspace_bytes, uint8_t *chars, long *str_off, hipStream_t stream);
+
 /* ---- Video self-training merge (s2d_amd/selftrain_video.py, csrc/selftrain_video.hip).  The rule is this project's own: the image
  * merge above carried to tubes (whole tracks); the reference has no video merge.  Both calls handle a CHUNK of N videos of different
  * sizes and lengths in one launch.
@@ -1160,6 +1180,42 @@ int s2d_index_components_i32(const uint8_t *index, int N, int H, int W, int conn
                              hipStream_t stream);
 int s2d_index_filter_components_u8(const uint8_t *index, const int *labels, const int *area, int N, int H, int W, int min_area,
                                    int keep_largest, uint8_t *out, uint8_t *rgb, int *removed, void *workspace, hipStream_t stream);
+
+/* ---- connected components and cleanup of ragged bit planes (s2d_amd/plane_components.py) -------------------- */
+
+/* bits u32 [total_words] and plane DEVICE int64 [P][4] = {word0, H, W, 0} are a chunk as s2d_rle_decode_ragged fills it: plane p is
+ * H x W pixels, pixel i = y*W + x in word word0 + i/32, bit i%32; rows are not word-aligned, pixel (y, W-1) and pixel (y+1, 0) are
+ * flat neighbours and never join.  The padding bits of a plane's last word are ignored on input and 0 on output.  The planes of a
+ * chunk overlap as masks, so every plane is labelled on its own, all of them in one launch: tiles DEVICE int32 [n_tiles][3] =
+ * {plane, tile row, tile column} lists every tile of every plane once (built on the host; the grid is 1-D over it).  A table row that
+ * names no tile of a plane the buffer holds is skipped, as a plane row that does not fit the buffer is.
+ * s2d_plane_components_tile: the tile (th rows x tw columns) a workgroup labels locally before the tiles are merged.
+ * s2d_plane_components_workspace_bytes: the scratch either call below needs (any address; the calls align it themselves): 12 bytes
+ * per pixel position of the buffer and 8 per plane; S2D_ERR_ARG (-1) for a negative argument.
+ * s2d_plane_components_ragged labels the pixels whose bit equals value (0 or 1) under conn = 4 or 8.  labels and area are i32 arrays
+ * of 32 * total_words elements, pixel i of plane p at 32 * word0 + i (a 64-bit index); positions of no pixel hold 0.  labels = 0
+ * where the bit is not value, else 1 + the flat index i of the component's first pixel in its plane -- a name that depends on
+ * nothing but the plane, so a second call is bitwise equal.  area (may be NULL) holds the component's pixel count at its first pixel
+ * and 0 elsewhere.  With value = 0 padding bits and everything outside the plane are not pixels: they join nothing, add no area.
+ * s2d_plane_clean_ragged writes out = fill(filter(plane)) for every plane; out may be bits.  This rule is the project's own (the
+ * reference cleans nothing).  filter (min_area > 0 or keep_largest != 0): a component of set pixels under conn is kept iff area >=
+ * min_area and, with keep_largest, it is the largest of its plane, among equal areas the one with the lowest first pixel; every
+ * other set pixel becomes 0.  fill (max_hole_area > 0): the ZERO pixels of the filtered plane are labelled under the complementary
+ * connectivity (8 -> 4, 4 -> 8); a component none of whose pixels lies in row 0, row H-1, column 0 or column W-1 is a hole, and a
+ * hole of at most max_hole_area pixels becomes set.  removed i32 [P] / filled i32 [P] = pixels cleared / set per plane (zeroed by
+ * the call).  With all three options off the planes are copied with their padding zeroed.  Words of out that belong to no plane
+ * are not written.
+ * Tile-local union-find in LDS, lock-free merge across tile borders through agent-scope atomics (a link only ever decreases),
+ * flatten; no workgroup waits for another and every atomic is an integer one, so results do not depend on the order of execution.
+ * The calls only enqueue.  conn other than 4 or 8, value other than 0 or 1, a negative size or area, a NULL pointer other than area
+ * (components) or tiles with n_tiles = 0, or a misaligned array return S2D_ERR_ARG before anything is launched. */
+int s2d_plane_components_tile(int *th, int *tw);
+long s2d_plane_components_workspace_bytes(long total_words, int P);
+int s2d_plane_components_ragged(const uint32_t *bits, const long *plane, int P, long total_words, int value, int conn,
+                                const int *tiles, int n_tiles, int *labels, int *area, void *workspace, hipStream_t stream);
+int s2d_plane_clean_ragged(const uint32_t *bits, const long *plane, int P, long total_words, int conn, int min_area,
+                           int keep_largest, int max_hole_area, const int *tiles, int n_tiles, uint32_t *out, int *removed,
+                           int *filled, void *workspace, hipStream_t stream);
 
 #ifdef __cplusplus
 }

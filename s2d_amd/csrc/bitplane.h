@@ -1,6 +1,6 @@
 // Device and host pieces shared by the kernels that work on packed bit planes: mask_counts.hip, coco_eval.hip and
 // selftrain_video.hip (pair popcounts), mask_counts.hip and rle_ragged.hip (plane areas), mask_boundary.hip and davis_eval.hip
-// (morphology on rows that are not word-aligned).
+// (morphology on rows that are not word-aligned), rle_ragged.hip and plane_components.hip (the ragged plane table).
 //
 // THE PLANE LAYOUT.  A plane of H x W pixels is FLAT: pixel i = y * W + x -> word i / 32, bit i % 32, ceil(H * W / 32) words (what
 // s2d_pack_mask_bits_u8 and s2d_rle_decode_bits write), so rows are not word-aligned unless W % 32 == 0.  The padding bits of a
@@ -107,6 +107,29 @@ __device__ __forceinline__ void store_row_word(uint32_t *__restrict__ op, int y,
         const unsigned int hi = o ? v >> (32 - o) : 0u;
         if (hi) atomicOr(&op[(P >> 5) + 1], hi);
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------ ragged plane table
+// Row p of the table plane int64 [P][4] = {word0, H, W, 0} of a chunk of planes of different sizes over one flat buffer of
+// total_words words (rle_ragged.hip, plane_components.hip).  ok = the buffer holds the plane: a row with H or W < 1, H*W >= 2^31 or
+// words outside [0, total_words) is skipped by every kernel that reads the table.
+struct PlaneRow {
+    long word0, wpp;
+    int H, W;
+    bool ok;
+};
+
+__device__ __forceinline__ PlaneRow plane_row(const long *__restrict__ plane, int p, long total_words)
+{
+    const long *r = plane + 4L * p;
+    PlaneRow q;
+    const long H = r[1], W = r[2];
+    q.word0 = r[0];
+    q.ok = H >= 1 && W >= 1 && H < (1L << 31) && W < (1L << 31) && H * W < (1L << 31);
+    q.H = (int)H; q.W = (int)W;
+    q.wpp = q.ok ? (H * W + 31) / 32 : 0;
+    q.ok = q.ok && q.word0 >= 0 && q.word0 <= total_words - q.wpp;
+    return q;
 }
 
 // ------------------------------------------------------------------------------------------------------------ 192-bit row windows

@@ -8,29 +8,16 @@
 // which is the COCO chunk layout (include/s2d_hip.h, "Ragged layout"), so s2d_coco_mask_iou_ragged reads the decoded buffer in place.
 // A row the buffer cannot hold (H or W < 1, H*W >= 2^31, words outside [0, total_words)) is skipped by every kernel: nothing is read
 // or written for it.  The host checks the table before the call; the kernels do not rely on that.
+//
+// The way back, bit planes -> RLE strings, is the dual: s2d_rle_count_ragged_u32 and s2d_rle_positions_ragged_u32 run the bodies of
+// s2d_rle_count_u8 / s2d_rle_positions_u8 (rle_encode.h) over a SELECTION of planes, sel int32 [S] (only the planes a cleanup changed
+// are encoded again), reading pixels from the flat planes; s2d_rle_strings_ragged (rle.hip, beside the string kernels it launches)
+// takes each plane's own H*W for the last run.
 #include "bitplane.h"
+#include "rle_encode.h"
 #include "rle_planes.h"
 
 namespace {
-
-struct PlaneRow {
-    long word0, wpp;
-    int H, W;
-    bool ok;
-};
-
-__device__ __forceinline__ PlaneRow plane_row(const long *__restrict__ plane, int p, long total_words)
-{
-    const long *r = plane + 4L * p;
-    PlaneRow q;
-    const long H = r[1], W = r[2];
-    q.word0 = r[0];
-    q.ok = H >= 1 && W >= 1 && H < (1L << 31) && W < (1L << 31) && H * W < (1L << 31);
-    q.H = (int)H; q.W = (int)W;
-    q.wpp = q.ok ? (H * W + 31) / 32 : 0;
-    q.ok = q.ok && q.word0 >= 0 && q.word0 <= total_words - q.wpp;
-    return q;
-}
 
 // rle_parse_kernel with the clamp taken from the plane's own size
 __global__ __launch_bounds__(RLE_PARSE_T) void rle_parse_ragged_kernel(const uint8_t *__restrict__ chars, const long *__restrict__ str_off,
@@ -87,6 +74,38 @@ __global__ __launch_bounds__(256) void plane_areas_ragged_kernel(const uint32_t 
         return;
     }
     plane_popcount(bits + q.word0, q.wpp, area + blockIdx.x);
+}
+
+// rle_count_kernel / rle_positions_kernel (rle.hip) with the mask taken from the plane table: workgroup s encodes plane sel[s]; its
+// column offsets start at col0[s] (the widths of the selection before it, summed on the host).  A selection entry that names no plane
+// the buffer holds has no boundaries, area 0 and a zero box, and nothing else is read or written for it.
+__global__ __launch_bounds__(RLE_ENC_T) void rle_count_ragged_kernel(const uint32_t *__restrict__ bits, const long *__restrict__ plane,
+                                                                     int P, long total_words, const int *__restrict__ sel,
+                                                                     const long *__restrict__ col0, int *__restrict__ col_off,
+                                                                     int *__restrict__ nbound, int *__restrict__ area, int *__restrict__ bbox)
+{
+    const int s = blockIdx.x, f = sel[s];
+    PlaneRow q;
+    q.ok = f >= 0 && f < P;
+    if (q.ok) q = plane_row(plane, f, total_words);
+    if (!q.ok) {                                            // uniform over the workgroup
+        if (threadIdx.x == 0) nbound[s] = area[s] = 0;
+        if (threadIdx.x < 4) bbox[4L * s + threadIdx.x] = 0;
+        return;
+    }
+    rle_count_body(RleBitFrame(bits + q.word0, q.wpp, q.W), q.H, q.W, col_off + col0[s], nbound + s, area + s, bbox + 4L * s);
+}
+
+__global__ __launch_bounds__(RLE_ENC_T) void rle_positions_ragged_kernel(const uint32_t *__restrict__ bits, const long *__restrict__ plane,
+                                                                         int P, long total_words, const int *__restrict__ sel,
+                                                                         const long *__restrict__ col0, const int *__restrict__ col_off,
+                                                                         const long *__restrict__ frame_off, int *__restrict__ positions)
+{
+    const int s = blockIdx.x, f = sel[s];
+    if (f < 0 || f >= P) return;
+    const PlaneRow q = plane_row(plane, f, total_words);
+    if (!q.ok) return;
+    rle_positions_body(RleBitFrame(bits + q.word0, q.wpp, q.W), q.H, q.W, col_off + col0[s], positions + frame_off[s]);
 }
 
 constexpr int KEEP_T = 64;
@@ -155,6 +174,30 @@ int s2d_mask_plane_areas_ragged_u32(const uint32_t *bits, const long *plane, int
     if (P == 0) return S2D_OK;
     if (!bits || !plane || !area) return S2D_ERR_ARG;
     hipLaunchKernelGGL(plane_areas_ragged_kernel, dim3(P), dim3(256), 0, stream, bits, plane, total_words, area);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_rle_count_ragged_u32(const uint32_t *bits, const long *plane, int P, long total_words, const int *sel, int S, const long *col0,
+                             int *col_off, int *nbound, int *area, int *bbox, hipStream_t stream)
+{
+    if (P < 0 || S < 0 || total_words < 0) return S2D_ERR_ARG;
+    if (S == 0) return S2D_OK;
+    if (!bits || !plane || !sel || !col0 || !col_off || !nbound || !area || !bbox) return S2D_ERR_ARG;
+    hipLaunchKernelGGL(rle_count_ragged_kernel, dim3(S), dim3(RLE_ENC_T), 0, stream, bits, plane, P, total_words, sel, col0, col_off, nbound,
+                       area, bbox);
+    S2D_CHECK_LAUNCH();
+    return S2D_OK;
+}
+
+int s2d_rle_positions_ragged_u32(const uint32_t *bits, const long *plane, int P, long total_words, const int *sel, int S, const long *col0,
+                                 const int *col_off, const long *frame_off, int *positions, hipStream_t stream)
+{
+    if (P < 0 || S < 0 || total_words < 0) return S2D_ERR_ARG;
+    if (S == 0) return S2D_OK;
+    if (!bits || !plane || !sel || !col0 || !col_off || !frame_off || !positions) return S2D_ERR_ARG;
+    hipLaunchKernelGGL(rle_positions_ragged_kernel, dim3(S), dim3(RLE_ENC_T), 0, stream, bits, plane, P, total_words, sel, col0, col_off,
+                       frame_off, positions);
     S2D_CHECK_LAUNCH();
     return S2D_OK;
 }

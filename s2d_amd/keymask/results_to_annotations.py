@@ -11,7 +11,10 @@ The RLE strings are decoded on the device (ytvis_eval.decode_frames) and the box
 (s2d_mask_plane_bbox_u32, s2d_mask_plane_areas_u32).
 
     python -m s2d_amd.keymask.results_to_annotations --annotation-file merged.json --gt-annotation-file gt.json \\
-        --results-file results.json --score-threshold 0.75 --output-dir D --output-filename NAME
+        --results-file results.json --score-threshold 0.75 --output-dir D --output-filename NAME \\
+        [--min-component-area N] [--keep-largest] [--fill-holes N|all] [--component-connectivity 4|8]
+
+The four cleanup options (s2d_amd/clean_annotations.py) are this project's own and off by default.
 """
 import argparse
 import json
@@ -54,7 +57,9 @@ def convert(merged, gt, results, score_threshold=0.75, bbox_area_fn=device_bboxe
 
 
 def convert_files(annotation_file, gt_annotation_file, results_file, score_threshold, output_dir, filename,
-                  bbox_area_fn=device_bboxes_areas):
+                  bbox_area_fn=device_bboxes_areas, cleanup=None):
+    """cleanup: a clean_annotations.cleanup_options dict; when it asks for anything the masks of the new document are cleaned just
+    before it is written (this project's own; the reference cleans nothing)"""
     with open(annotation_file) as fh:
         merged = json.load(fh)
     with open(results_file) as fh:
@@ -62,6 +67,9 @@ def convert_files(annotation_file, gt_annotation_file, results_file, score_thres
     with open(gt_annotation_file) as fh:
         gt = json.load(fh)
     doc, low = convert(merged, gt, results, score_threshold, bbox_area_fn)
+    if cleanup:
+        from ..clean_annotations import clean_merged
+        doc = clean_merged(doc, cleanup)
     os.makedirs(output_dir, exist_ok=True)
     path = os.path.join(output_dir, f"{filename}.json")
     with open(path, "w") as fh:
@@ -79,9 +87,10 @@ def main(argv=None):
     ap.add_argument("--score-threshold", type=float, default=0.75)
     ap.add_argument("--output-dir", required=True)
     ap.add_argument("--output-filename", required=True)
-    a = ap.parse_args(argv)
+    from ..clean_annotations import add_cleanup_arguments, cleanup_options
+    a = add_cleanup_arguments(ap).parse_args(argv)
     print(convert_files(a.annotation_file, a.gt_annotation_file, a.results_file, a.score_threshold, a.output_dir,
-                        a.output_filename))
+                        a.output_filename, cleanup=cleanup_options(a)))
 
 
 if __name__ == "__main__":

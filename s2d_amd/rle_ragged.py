@@ -1,5 +1,6 @@
-"""COCO RLE -> bit planes for a CHUNK of images of different sizes: the host staging of the whole chunk at once and three library
-calls per chunk -- parse, decode, tight boxes -- however many images it holds (csrc/rle_ragged.hip).  The per-image path
+"""COCO RLE <-> bit planes for a CHUNK of images of different sizes.  decode_ragged: the host staging of the whole chunk at once and
+three library calls per chunk -- parse, decode, tight boxes -- however many images it holds (csrc/rle_ragged.hip); encode_ragged,
+the way back: count, positions, strings for a selection of the chunk's planes, three calls as well.  The per-image path
 (ytvis_eval.stage_rle / decode_staged / plane_bboxes, what coco_eval.decode_segmentations calls) costs four small uploads and two or
 three calls per image; on very many small images with a handful of masks each that is what the time goes to.
 
@@ -16,7 +17,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-LIB_CALLS = Counter()          # library calls made by decode_ragged, by export name
+LIB_CALLS = Counter()          # library calls made by decode_ragged and encode_ragged, by export name
 
 
 def _lib_call(name, *args):
@@ -147,3 +148,49 @@ def decode_ragged(staged, device=None, bbox_out=None):
     _lib_call("s2d_mask_plane_bbox_ragged_u32", bits, plane, s.P, s.words, bbox, st)
     out.plane_dev = plane
     return out
+
+
+def encode_ragged(bits, staged_or_plane_table, sel):
+    """the way back: bits int32 CUDA [words], the flat buffer of a chunk; staged_or_plane_table: what stage_rle_ragged returned, or a
+    plane table int64 numpy [P, 4] = {word0, H, W, 0}; sel: the planes to encode, in any order -> (list of {"size": [H, W], "counts":
+    str} in the order of sel, areas int64 numpy [S], boxes float64 numpy [S, 4] = x, y, w, h).  One upload, three library calls and
+    two read-backs (the boundary counts, then the strings) however many planes are selected.  A plane's string is byte for byte what
+    s2d_amd.rle.encode writes for the same mask: both run the device bodies of csrc/rle_encode.h."""
+    import torch
+    from . import ops
+    from ._lib import lib
+    plane = np.ascontiguousarray(getattr(staged_or_plane_table, "plane", staged_or_plane_table), np.int64).reshape(-1, 4)
+    sel = np.ascontiguousarray(sel, np.int32).reshape(-1)
+    P, S = len(plane), len(sel)
+    if S == 0:
+        return [], np.zeros((0,), np.int64), np.zeros((0, 4), np.float64)
+    if bits.dtype != torch.int32 or bits.dim() != 1 or not bits.is_cuda or not bits.is_contiguous():
+        raise ValueError(f"encode_ragged needs the flat int32 CUDA buffer of a chunk, got {bits.dtype} {tuple(bits.shape)}")
+    if sel.min() < 0 or sel.max() >= P:
+        raise ValueError(f"encode_ragged: a selected plane outside [0, {P})")
+    rows = plane[sel]
+    H, W = rows[:, 1], rows[:, 2]
+    if H.min() < 1 or W.min() < 1 or (H * W).max() >= 1 << 31 or rows[:, 0].min() < 0 or (rows[:, 0] + (H * W + 31) // 32).max() > bits.numel():
+        raise ValueError(f"encode_ragged: a selected plane does not fit the buffer of {bits.numel()} words")
+    col0 = np.cumsum(W) - W
+    dev, st = bits.device, ops._stream()
+    plane_d, sel_d, col0_d = _upload([plane, sel, col0], dev)
+    col_off = torch.empty((int(W.sum()),), device=dev, dtype=torch.int32)
+    nb = torch.empty((S,), device=dev, dtype=torch.int32)
+    area = torch.empty((S,), device=dev, dtype=torch.int32)
+    bbox = torch.empty((S, 4), device=dev, dtype=torch.int32)
+    _lib_call("s2d_rle_count_ragged_u32", bits, plane_d, P, bits.numel(), sel_d, S, col0_d, col_off, nb, area, bbox, st)
+    frame_off = torch.zeros((S + 1,), device=dev, dtype=torch.int64)
+    torch.cumsum(nb, 0, out=frame_off[1:])
+    total = int(frame_off[-1])                                            # read-back 1: sizes the outputs
+    ncounts = total + S
+    pos = torch.empty((max(total, 1),), device=dev, dtype=torch.int32)
+    _lib_call("s2d_rle_positions_ragged_u32", bits, plane_d, P, bits.numel(), sel_d, S, col0_d, col_off, frame_off, pos, st)
+    ws = torch.empty((lib().call("s2d_rle_strings_ragged_workspace_bytes", ncounts),), device=dev, dtype=torch.uint8)
+    chars = torch.empty((7 * ncounts,), device=dev, dtype=torch.uint8)
+    str_off = torch.empty((S + 1,), device=dev, dtype=torch.int64)
+    _lib_call("s2d_rle_strings_ragged", pos, frame_off, plane_d, P, sel_d, S, ncounts, ws, ws.numel(), chars, str_off, st)
+    so = str_off.cpu().numpy()                                            # read-back 2
+    buf = chars[:int(so[-1])].cpu().numpy().tobytes()
+    rles = [{"size": [int(H[s]), int(W[s])], "counts": buf[so[s]:so[s + 1]].decode("ascii")} for s in range(S)]
+    return rles, area.cpu().numpy().astype(np.int64), bbox.cpu().numpy().astype(np.float64)

@@ -1,6 +1,7 @@
 """Image self-training rounds: the previous round's annotation file + this round's predictions -> the next round's annotation file.
 
     python -m s2d_amd.selftrain --new-pred OUT/coco_instances_results.json --prev-ann round0.json --save-path round1.json [--threshold 0.7]
+        [--min-component-area N] [--keep-largest] [--fill-holes N|all] [--component-connectivity 4|8]
 
 The step that closes the image loop (train --train-format coco_image -> evaluate --test-format coco_image -> selftrain -> train), as
 keymask.results_to_annotations closes the video loop.  Restates the reference's model_training/cutler/tools/get_self_training_ann.py
@@ -43,7 +44,10 @@ Where this differs from the reference, on purpose:
     NaN compares false, and the previous mask is dropped here too;
   * a polygon segmentation has no `size`: width / height take the image's [height, width] in the same swapped order (the reference
     cannot merge polygons at all: it indexes segmentation["size"]);
-  * the inputs are not modified: output annotations are copies.
+  * the inputs are not modified: output annotations are copies;
+  * the mask cleanup options (s2d_amd/clean_annotations.py; this project's own, off by default) clean the merged document's masks
+    just before it is written.  The merge and keep rules see the masks as they came, and with the options off the file and the
+    library calls are what they are without them.
 """
 import argparse
 import json
@@ -223,8 +227,9 @@ def merge_round(prev_doc, predictions, threshold=0.7, device=None, keep_fn=None,
     return out
 
 
-def merge_files(new_pred, prev_ann, save_path, threshold=0.7, device=None, keep_fn=None, seconds=None):
-    """the command line on paths -> the written document"""
+def merge_files(new_pred, prev_ann, save_path, threshold=0.7, device=None, keep_fn=None, seconds=None, cleanup=None):
+    """the command line on paths -> the written document.  cleanup: a clean_annotations.cleanup_options dict; when it asks for
+    anything the merged document's masks are cleaned just before it is written (area = bbox w * h, as every annotation here)"""
     t0 = time.perf_counter()
     with open(new_pred) as fh:
         predictions = json.load(fh)
@@ -232,6 +237,9 @@ def merge_files(new_pred, prev_ann, save_path, threshold=0.7, device=None, keep_
         prev_doc = json.load(fh)
     t_json = time.perf_counter() - t0
     doc = merge_round(prev_doc, predictions, threshold, device=device, keep_fn=keep_fn, seconds=seconds)
+    if cleanup:
+        from .clean_annotations import clean_merged
+        doc = clean_merged(doc, cleanup, area_rule="bbox", device=device)
     t0 = time.perf_counter()
     with open(save_path, "w") as fh:
         json.dump(doc, fh)
@@ -248,8 +256,9 @@ def main(argv=None):
     ap.add_argument("--save-path", type=str, default="DETECTRON2_DATASETS/imagenet/annotations/cutler_imagenet1k_train_r1.json",
                     help="Path to save the generated annotation file")
     ap.add_argument("--threshold", type=float, default=0.7, help="Confidence score thresholds")
-    a = ap.parse_args(argv)
-    doc = merge_files(a.new_pred, a.prev_ann, a.save_path, a.threshold)
+    from .clean_annotations import add_cleanup_arguments, cleanup_options
+    a = add_cleanup_arguments(ap).parse_args(argv)
+    doc = merge_files(a.new_pred, a.prev_ann, a.save_path, a.threshold, cleanup=cleanup_options(a))
     print("Done: {} images; {} anns.".format(len(doc["images"]), len(doc["annotations"])))
 
 

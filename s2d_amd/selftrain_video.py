@@ -311,8 +311,9 @@ def merge_round(prev_doc, results, videos_doc=None, threshold=0.75, frames="anno
 
 
 def merge_files(results_file, prev_ann, save_path, gt_annotation_file=None, threshold=0.75, frames="annotated", device=None,
-                device_fn=None, seconds=None):
-    """the command line on paths -> the written document"""
+                device_fn=None, seconds=None, cleanup=None):
+    """the command line on paths -> the written document.  cleanup: a clean_annotations.cleanup_options dict; when it asks for
+    anything the merged document's masks are cleaned just before it is written (the merge sees the masks as they came)"""
     t0 = time.perf_counter()
     with open(results_file) as fh:
         results = json.load(fh)
@@ -324,6 +325,9 @@ def merge_files(results_file, prev_ann, save_path, gt_annotation_file=None, thre
             gt = json.load(fh)
     t_json = time.perf_counter() - t0
     doc = merge_round(prev_doc, results, gt, threshold, frames, device=device, device_fn=device_fn, seconds=seconds)
+    if cleanup:
+        from .clean_annotations import clean_merged
+        doc = clean_merged(doc, cleanup, device=device)
     t0 = time.perf_counter()
     with open(save_path, "w") as fh:
         json.dump(doc, fh)
@@ -341,8 +345,9 @@ def main(argv=None):
     ap.add_argument("--score-threshold", type=float, default=0.75)
     ap.add_argument("--frames", choices=FRAME_SETS, default="annotated",
                     help="frames a previous track is compared on: those it annotates (default), or all (the YTVIS evaluator's IoU)")
-    a = ap.parse_args(argv)
-    doc = merge_files(a.results_file, a.prev_ann, a.save_path, a.gt_annotation_file, a.score_threshold, a.frames)
+    from .clean_annotations import add_cleanup_arguments, cleanup_options
+    a = add_cleanup_arguments(ap).parse_args(argv)
+    doc = merge_files(a.results_file, a.prev_ann, a.save_path, a.gt_annotation_file, a.score_threshold, a.frames, cleanup=cleanup_options(a))
     print("Done: {} videos; {} anns.".format(len(doc["videos"]), len(doc["annotations"])))
 
 
