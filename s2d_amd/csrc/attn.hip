@@ -905,8 +905,7 @@ int s2d_attn_mask_bits(const float *mask_logits, int ldq, int B, int Q, int T, i
     if (B == 0 || K == 0) return S2D_OK;
     if (K >= (1L << 31) - 8) return S2D_ERR_ARG;
     if (s2d_zero_async(unmasked, sizeof(uint32_t) * QW * B, stream) != S2D_OK) return S2D_ERR_LAUNCH;
-    static int dword_taps = -1;
-    if (dword_taps < 0) { const char *e = getenv("S2D_ATTN_MASK_DWORD_TAPS"); dword_taps = e ? atoi(e) : 0; }
+    static const int dword_taps = s2d_env_int("S2D_ATTN_MASK_DWORD_TAPS", 0);
     if (dword_taps && !compact) {          // regression variant (tests only), see attn_mask_kernel_dword_taps
         hipLaunchKernelGGL(attn_mask_kernel_dword_taps, dim3(cdiv(K, 8), B), dim3(256), 0, stream, mask_logits, ldq, Q, T, hm, wm, hl, wl,
                            bits, unmasked);
@@ -951,8 +950,7 @@ int s2d_masked_attn_backward_strided_f32(const float *q, const float *k, const f
     p.tiles_per_split = (tiles + p.S - 1) / p.S;
     p.qscale = 0.17677669529663687f * 1.4426950408889634f;
     p.dk = dk; p.dv = dv; p.dq_part = workspace; p.lddk = lddk; p.lddv = lddv;
-    static int mfma = -1;                                    // S2D_ATTN_BWD_MFMA=0: the two scalar fp32 kernels (A/B runs, tests)
-    if (mfma < 0) { const char *e = getenv("S2D_ATTN_BWD_MFMA"); mfma = e ? atoi(e) : 1; }
+    static const int mfma = s2d_env_int("S2D_ATTN_BWD_MFMA", 1);      // 0: the two scalar fp32 kernels (A/B runs, tests)
     if (mfma) {
         static S2dDevOnce attr;
         if (!attr.done()) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define S2D_OK 0
 #define S2D_ERR_ARG (-1)
@@ -40,6 +41,15 @@ struct S2dDevOnce {
 };
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// The one reader of the kernel switches (environment variables S2D_*; table in DESIGN.md "Switches"), in two spellings:
+//   static const int x = s2d_env_int(...);    read once per process (thread-safe static initialisation)
+//   s2d_env_int(...)                          read per call: tests and scripts switch it inside one process
+static inline int s2d_env_int(const char *name, int dflt)
+{
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 // Zero `bytes` bytes with a kernel on `stream`.  Used instead of hipMemsetAsync: the
 // runtime may run a memset on a different engine than the kernels around it, and with two streams sharing the GPU the

@@ -12,8 +12,8 @@
 // -> registers -> split (v_cvt_pk_bf16_f32, v_pk_add_f32) -> LDS rows of [16 words hi | 16 words lo | 4 pad]
 // (stride 36 words: conflict-free for ds_read_b128 fragment reads and the ds_write_b64 stores), double buffered.
 #include "gemm_epilogue.h"
+#include "gemm_route.h"
 #include "dropout.h"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -21,7 +21,7 @@ namespace {
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int BN = 128, BK = 32, ROWW = 36;  // LDS row = 36 words (144 B)
+constexpr int BN = GEMM_BN, BK = GEMM_BK, ROWW = 36;  // LDS row = 36 words (144 B)
 
 __device__ __forceinline__ void split4_bf16(const f32x4 v, u32x2 &hi, u32x2 &lo)
 {
@@ -815,7 +815,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(GemmParams p)
 // PH x 16 output pixels and BNT = 64 WNW output channels per workgroup, a wave = 64 pixels x 64 channels either way:
 //   <8, 2>: 8 x 16 patch x 128 channels (Cout > 64);  <16, 1>: 16 x 16 patch x 64 channels (Cout <= 64: the res2 bottlenecks'
 //   3 x 3 convolutions, which the implicit-GEMM 128 x 64 kernel ran at 234 TFLOP/s with 9 x the input traffic through L2).
-constexpr int HT_H = 8, HT_W = 16, HALO_W = HT_W + 2;
+constexpr int HT_H = HALO_PH, HT_W = HALO_PW, HALO_W = HT_W + 2;
 template <int PH, int WNW, bool PIPE>
 __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_halo_kernel(GemmParams p)
 {
@@ -1795,16 +1795,12 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x3_ws_kernel(GemmParams p)
 }
 
 template <bool CONV>
-int launch_f16_hi(const GemmParams &p, int batch, hipStream_t st)
+int launch_f16_hi(const GemmParams &p, const GemmRoute &r, int batch, hipStream_t st)
 {
     const size_t lds = sizeof(float) * 4 * 64 * 36;   // 36.9 KB: epilogue staging >= operand tiles (27.6 KB)
     const int nwg = cdiv(p.M, 128) * cdiv(p.N, 64);
-    static int pre = -1;
-    if (pre < 0) { const char *e = getenv("S2D_GEMM_HI_PRE"); pre = e ? atoi(e) : 1; }
-    // residual prefetch: short K (the 1 x 1 convolutions of res2 / res3 that close a bottleneck), vector epilogue, no gate
-    if (pre && p.Bsplit && p.res && !p.gate && p.K <= 4 * BK && ((p.N | p.ldc | p.ldr | p.res_cols) & 3) == 0)
-        hipLaunchKernelGGL((gemm_f16x3_hi_kernel<CONV, true, true>), dim3(nwg, batch), dim3(256), lds, st, p);
-    else if (p.Bsplit) hipLaunchKernelGGL((gemm_f16x3_hi_kernel<CONV, true>), dim3(nwg, batch), dim3(256), lds, st, p);
+    if (r.pre) hipLaunchKernelGGL((gemm_f16x3_hi_kernel<CONV, true, true>), dim3(nwg, batch), dim3(256), lds, st, p);
+    else if (r.bsplit) hipLaunchKernelGGL((gemm_f16x3_hi_kernel<CONV, true>), dim3(nwg, batch), dim3(256), lds, st, p);
     else hipLaunchKernelGGL((gemm_f16x3_hi_kernel<CONV, false>), dim3(nwg, batch), dim3(256), lds, st, p);
     S2D_CHECK_LAUNCH();
     return S2D_OK;
@@ -1827,7 +1823,6 @@ int launch_f16_v(const GemmParams &p, int batch, hipStream_t st)
     return S2D_OK;
 }
 
-constexpr int WS_CONST_N = 16384;
 __global__ void ws_constants_kernel(float *z, float *o)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -1875,22 +1870,22 @@ int launch_f16_ws_v(const GemmParams &p, hipStream_t st)
     return S2D_OK;
 }
 
-template <bool CONV, bool BSPLIT, bool DROP>
-int launch_f16_ws(const GemmParams &p, hipStream_t st)
+template <bool CONV, bool DROP, bool ASPLIT>
+int launch_f16_ws(const GemmParams &p, const GemmRoute &r, hipStream_t st)
 {
-    return p.res ? launch_f16_ws_v<CONV, BSPLIT, DROP, true>(p, st) : launch_f16_ws_v<CONV, BSPLIT, DROP, false>(p, st);
+    if (r.bsplit) return r.res ? launch_f16_ws_v<CONV, true, DROP, true, ASPLIT>(p, st) : launch_f16_ws_v<CONV, true, DROP, false, ASPLIT>(p, st);
+    if constexpr (ASPLIT) return S2D_ERR_ARG;                 // a pre-split A comes with a static B image (the route guarantees it)
+    else return r.res ? launch_f16_ws_v<CONV, false, DROP, true>(p, st) : launch_f16_ws_v<CONV, false, DROP, false>(p, st);
 }
 
 template <bool CONV, bool PIPE>
-int launch_f16(const GemmParams &p, int batch, hipStream_t st)
+int launch_f16(const GemmParams &p, const GemmRoute &r, int batch, hipStream_t st)
 {
-    return p.Bsplit ? launch_f16_v<CONV, PIPE, true>(p, batch, st) : launch_f16_v<CONV, PIPE, false>(p, batch, st);
+    return r.bsplit ? launch_f16_v<CONV, PIPE, true>(p, batch, st) : launch_f16_v<CONV, PIPE, false>(p, batch, st);
 }
 
-int launch_conv7x7s2_stem(const GemmParams &p, hipStream_t st)
+int launch_conv7x7s2_stem(const GemmParams &p, int ph, hipStream_t st)
 {
-    static int ph = -1;
-    if (ph < 0) { const char *e = getenv("S2D_CONV_STEM_PH"); ph = e ? atoi(e) : 8; }
     const size_t lds16 = sizeof(float) * 4 * 64 * 68, lds8 = sizeof(float) * 4 * 32 * 68;       // epilogue staging >= halo planes + two weight buffers
     static S2dDevOnce attr_set;
     if (!attr_set.done()) {
@@ -1905,14 +1900,8 @@ int launch_conv7x7s2_stem(const GemmParams &p, hipStream_t st)
     return S2D_OK;
 }
 
-int launch_conv3x3_halo(const GemmParams &pin, hipStream_t st)
+int launch_conv3x3_halo(const GemmParams &p, const GemmRoute &r, hipStream_t st)
 {
-    const GemmParams &p = pin;
-    // opt-in (S2D_CONV_HALO_PIPE=1, read per call): measured +2.6 % on 942 080 x 256 x 2 304, -1..-2 % on the smaller 3 x 3 shapes, -9 % on the
-    // 64-channel form (scripts/mb_conv3_pipe.py, profiles/r5_experiments/not_adopted.txt): at two waves per SIMD the fragment latency the
-    // round-4 form exposes is already covered by the other wave
-    int pipe = 0;
-    if (const char *e = getenv("S2D_CONV_HALO_PIPE")) pipe = atoi(e);
     const size_t lds = sizeof(float) * 4 * 64 * 68;           // epilogue staging (69.6 KB) >= halo + two weight buffers (62.8 / 65.1 KB)
     static S2dDevOnce attr_set;
     if (!attr_set.done()) {
@@ -1922,13 +1911,13 @@ int launch_conv3x3_halo(const GemmParams &pin, hipStream_t st)
         attr_set.mark();
     }
     const int imgs = p.M / (p.Hin * p.Win);
-    if (p.N <= 64) {
+    if (r.ph == 16) {
         const int nwg = imgs * cdiv(p.Hin, 16) * cdiv(p.Win, HT_W);
-        if (pipe) hipLaunchKernelGGL((conv3x3_f16x3_halo_kernel<16, 1, true>), dim3(nwg), dim3(256), lds, st, p);
+        if (r.pipe) hipLaunchKernelGGL((conv3x3_f16x3_halo_kernel<16, 1, true>), dim3(nwg), dim3(256), lds, st, p);
         else hipLaunchKernelGGL((conv3x3_f16x3_halo_kernel<16, 1, false>), dim3(nwg), dim3(256), lds, st, p);
     } else {
         const int nwg = imgs * cdiv(p.Hin, HT_H) * cdiv(p.Win, HT_W) * cdiv(p.N, BN);
-        if (pipe) hipLaunchKernelGGL((conv3x3_f16x3_halo_kernel<8, 2, true>), dim3(nwg), dim3(256), lds, st, p);
+        if (r.pipe) hipLaunchKernelGGL((conv3x3_f16x3_halo_kernel<8, 2, true>), dim3(nwg), dim3(256), lds, st, p);
         else hipLaunchKernelGGL((conv3x3_f16x3_halo_kernel<8, 2, false>), dim3(nwg), dim3(256), lds, st, p);
     }
     S2D_CHECK_LAUNCH();
@@ -1950,12 +1939,6 @@ int launch_w128_v(const GemmParams &p, int batch, hipStream_t st)
     hipLaunchKernelGGL((gemm_bf16x3_w128_kernel<CONV, BSPLIT>), dim3(nwg, batch), dim3(256), lds, st, p);
     S2D_CHECK_LAUNCH();
     return S2D_OK;
-}
-
-template <bool CONV>
-int launch_w128(const GemmParams &p, int batch, hipStream_t st)
-{
-    return p.Bsplit ? launch_w128_v<CONV, true>(p, batch, st) : launch_w128_v<CONV, false>(p, batch, st);
 }
 
 template <int WM, bool CONV>
@@ -2027,121 +2010,51 @@ int s2d_split_weights_launch(const float *W, int N, int K, long ldw, unsigned in
     return S2D_OK;
 }
 
-// Where the row-resident kernel (gemm_rows.hip) is taken by default: the shape classes in which it measured >= 5 % faster than the tiled
-// kernels in isolation (scripts/mb_gemm_rows.py, profiles/gemm_rows/per_shape.txt; time tiled / time row-resident):
-//   58 880 x 1024 x 256  1.48     235 520 x 768 x 256  1.17     309 120 x 544 x 256  1.21     235 520 x 512 x 128  1.11     942 080 x 256 x 256  1.08
-//   942 080 x 256 x 64   0.97     942 080 x 128 x 256  0.94      58 880 x 768 x 256  1.00      14 720 x 768 x 256  0.56
-// What it saves per row is the re-load and re-split of K values for every 64-column tile after the first, ~ N . K: the winners have
-// N . K >= 64 K values, the two large-M losers 16 K and 32 K.  It launches M / 128 workgroups that run two to a CU and have a
-// serial prologue each (load, split, first weight stage), so it needs M >= 64 K rows = two full rounds of the chip; below that only
-// the widest output still wins (58 880 rows: N = 1024 yes, N = 768 a tie), and at 115 workgroups it loses to the tiled kernels' 1 380.
-static bool gemm_rows_wins(const GemmParams &p)
+// The switches of the dense dispatch (gemm_route.h), each at the time it has always been read: S2D_GEMM_ROWS and S2D_CONV_HALO_PIPE per
+// call (tests and scripts/mb_gemm_rows.py, mb_conv3_pipe.py switch them inside one process), the rest once per process
+static GemmSwitches read_gemm_switches()
 {
-    if (p.M >= 65536) return (long)p.N * p.K >= 65536;
-    return p.M >= 32768 && p.N >= 1024 && p.K >= 256;
+    GemmSwitches s;
+    static const int small = s2d_env_int("S2D_GEMM_SMALL", s.small), ws = s2d_env_int("S2D_GEMM_WS", s.ws), hi = s2d_env_int("S2D_GEMM_HI", s.hi),
+                     hi_pre = s2d_env_int("S2D_GEMM_HI_PRE", s.hi_pre), pipe = s2d_env_int("S2D_GEMM_PIPE", s.pipe), w128 = s2d_env_int("S2D_GEMM_W128", s.w128),
+                     wm = s2d_env_int("S2D_GEMM_WM", s.wm), halo = s2d_env_int("S2D_CONV_HALO", s.halo), halo64 = s2d_env_int("S2D_CONV_HALO64", s.halo64),
+                     stem = s2d_env_int("S2D_CONV_STEM", s.stem), stem_ph = s2d_env_int("S2D_CONV_STEM_PH", s.stem_ph);
+    s.small = small; s.ws = ws; s.hi = hi; s.hi_pre = hi_pre; s.pipe = pipe; s.w128 = w128; s.wm = wm; s.halo = halo; s.halo64 = halo64; s.stem = stem; s.stem_ph = stem_ph;
+    s.rows = s2d_env_int("S2D_GEMM_ROWS", s.rows);
+    s.halo_pipe = s2d_env_int("S2D_CONV_HALO_PIPE", s.halo_pipe);
+    return s;
 }
 
 int s2d_launch_gemm_bf16x3(const GemmParams &pin, bool conv, int batch, hipStream_t st, int f16)
 {
     GemmParams p = pin;
-    const long bA = conv ? (long)(p.M / ((long)p.Hout * p.Wout)) * p.Hin * p.Win * p.Cin * 4L : ((long)(p.M - 1) * p.lda + p.K) * 4L;
-    const long bB = ((long)(p.N - 1) * p.ldb + p.K) * 4L;
-    if (bA > 0xFFFFFF00L || bB > 0xFFFFFF00L) return S2D_ERR_ARG;   // 32-bit buffer offsets
-    p.bytesA = (unsigned int)bA; p.bytesB = (unsigned int)bB;
-    if (p.Bsplit) {
-        if ((batch > 1 && p.sB != 0) || (long)p.N * ((p.K + 31) / 32) * 128L > 0xFFFFFF00L) return S2D_ERR_ARG;
-        p.kblocks = (p.K + 31) / 32;
+    if (!s2d_gemm_extents(p, conv, batch)) return S2D_ERR_ARG;
+    const GemmSwitches sw = read_gemm_switches();
+    const GemmRoute r = s2d_gemm_route(p, conv, batch, f16, sw);
+    switch (r.family) {
+    case GEMM_ERR_ARG: break;
+    case GEMM_ROWS: return s2d_launch_gemm_rows(p, sw, st);
+    case GEMM_SMALL_M: return s2d_launch_gemm_small_m(p, st);
+    case GEMM_F16_WS:
+        if (r.asplit) return r.drop ? launch_f16_ws<false, true, true>(p, r, st) : launch_f16_ws<false, false, true>(p, r, st);
+        if (r.conv) return launch_f16_ws<true, false, false>(p, r, st);
+        return r.drop ? launch_f16_ws<false, true, false>(p, r, st) : launch_f16_ws<false, false, false>(p, r, st);
+    case GEMM_F16_HI: return r.conv ? launch_f16_hi<true>(p, r, batch, st) : launch_f16_hi<false>(p, r, batch, st);
+    case GEMM_F16:
+        if (r.drop) return r.bsplit ? launch_f16_v<false, true, true, true>(p, batch, st) : launch_f16_v<false, true, false, true>(p, batch, st);
+        if (r.pipe) return r.conv ? launch_f16<true, true>(p, r, batch, st) : launch_f16<false, true>(p, r, batch, st);
+        return r.conv ? launch_f16<true, false>(p, r, batch, st) : launch_f16<false, false>(p, r, batch, st);
+    case GEMM_CONV3X3_HALO: return launch_conv3x3_halo(p, r, st);
+    case GEMM_CONV7X7S2_STEM: return launch_conv7x7s2_stem(p, r.ph, st);
+    case GEMM_W128: return r.bsplit ? launch_w128_v<false, true>(p, batch, st) : launch_w128_v<false, false>(p, batch, st);
+    case GEMM_T2: return r.conv ? launch_t<2, true>(p, batch, st) : launch_t<2, false>(p, batch, st);
+    case GEMM_T4: return r.conv ? launch_t<4, true>(p, batch, st) : launch_t<4, false>(p, batch, st);
     }
-    if (!f16 && (p.Asplit || p.gate || p.drop_thresh)) return S2D_ERR_ARG;
-    // row-resident kernel (gemm_rows.hip; S2D_GEMM_ROWS, read per call: 0 never, 2 every launch it takes, 1 = default: by the rule below)
-    int rows = 1;
-    if (const char *e = getenv("S2D_GEMM_ROWS")) rows = atoi(e);
-    if (rows && s2d_gemm_rows_ok(p, conv, batch, f16) && (rows == 2 || gemm_rows_wins(p))) return s2d_launch_gemm_rows(p, st);
-    if (s2d_gemm_small_m_ok(p, conv, batch, f16)) return s2d_launch_gemm_small_m(p, st);      // the video decoder's query side (M = 200)
-    static int ws = -1;
-    if (ws < 0) { const char *e = getenv("S2D_GEMM_WS"); ws = e ? atoi(e) : 0; }
+    return S2D_ERR_ARG;
+}
 
-    // wave-specialised persistent kernel: one batch slice, >= 7 k-tiles (the previous tile's write-back is spread over the
-    // k-loop), 16-B rows for the row-wise epilogue, 32-bit buffer offsets into C and the residual
-    const long bC = ((long)(p.M - 1) * p.ldc + p.N) * 4L, bR = p.res ? ((long)((p.res_rows ? p.res_rows : p.M) - 1) * p.ldr + p.N) * 4L : 0;
-    const bool ws_ok = ws && f16 && batch == 1 && !p.gate && p.N <= WS_CONST_N && (conv || !p.scale) && p.K >= 7 * BK - (BK - 1) && ((p.N | p.ldc | p.ldr | p.res_cols) & 3) == 0 &&
-                       (conv ? (p.Cin % 4 == 0 && (p.Bsplit || p.K % BK == 0)) : p.K % BK == 0) &&
-                       bC <= 0xFFFFFF00L && bR <= 0xFFFFFF00L && (!p.res_rows || p.res_rows >= 64) &&
-                       (!p.drop_thresh || (((p.N | p.ldc) & 7) == 0 && (!p.res || ((p.ldr | p.res_cols) & 7) == 0)));
-    if (p.Asplit) {
-        // pre-split A: only the wave-specialised kernel reads it (its producers copy); the caller guarantees a static B image
-        const bool ok = f16 && !conv && batch == 1 && p.Bsplit && !p.scale && p.N <= WS_CONST_N && p.K >= 7 * BK - (BK - 1) && p.K % BK == 0 &&
-                        ((p.N | p.ldc | p.ldr | p.res_cols) & 3) == 0 && bC <= 0xFFFFFF00L && bR <= 0xFFFFFF00L &&
-                        (long)p.M * p.kblocks * 128L <= 0xFFFFFF00L && (!p.res_rows || p.res_rows >= 64) &&
-                        (!p.drop_thresh || (((p.N | p.ldc) & 7) == 0 && (!p.res || ((p.ldr | p.res_cols) & 7) == 0)));
-        if (!ok) return S2D_ERR_ARG;
-        if (p.drop_thresh) return p.res ? launch_f16_ws_v<false, true, true, true, true>(p, st) : launch_f16_ws_v<false, true, true, false, true>(p, st);
-        return p.res ? launch_f16_ws_v<false, true, false, true, true>(p, st) : launch_f16_ws_v<false, true, false, false, true>(p, st);
-    }
-    if (ws_ok && !conv && (ws == 2 || (p.Bsplit && (long)cdiv(p.M, 128) * cdiv(p.N, BN) >= 512))) {
-        if (p.drop_thresh) return p.Bsplit ? launch_f16_ws<false, true, true>(p, st) : launch_f16_ws<false, false, true>(p, st);
-        return p.Bsplit ? launch_f16_ws<false, true, false>(p, st) : launch_f16_ws<false, false, false>(p, st);
-    }
-    if (ws_ok && conv && !p.drop_thresh && (ws == 2 || (long)cdiv(p.M, 128) * cdiv(p.N, BN) >= 512)) {
-        return p.Bsplit ? launch_f16_ws<true, true, false>(p, st) : launch_f16_ws<true, false, false>(p, st);
-    }
-    if (p.gate && (!f16 || batch != 1 || p.drop_thresh || ((p.N | p.ldc | p.ldr | p.res_cols | p.ldg) & 3))) return S2D_ERR_ARG;
-    if (p.drop_thresh) {
-        // fused dropout lives in the vector epilogue of the pipelined 128x128 split-fp16 kernel (the three encoder-layer
-        // GEMMs that carry it all dispatch there): 8-column mask blocks, 16-B aligned rows
-        if (!f16 || conv || ((p.N | p.ldc) & 7) || (p.res && (((p.ldr | p.res_cols) & 7)))) return S2D_ERR_ARG;
-        return p.Bsplit ? launch_f16_v<false, true, true, true>(p, batch, st) : launch_f16_v<false, true, false, true>(p, batch, st);
-    }
-    // 256-row tiles only when they still fill the chip
-    if (f16) {
-        // measured (scripts/mb_shapes.py, mb_pipe.py): the pipelined 128x128 kernel wins on the spatial convolutions and, once
-        // the weights arrive pre-split, on the GEMMs with K >= 512 (+9..23 %) and on K = 256 when 128-wide tiles waste no
-        // more columns than 64-wide ones; the 16-waves/CU 128x64 kernel keeps the short-K (<= 128: two to four k-steps,
-        // all prologue/epilogue), narrow (N <= 64) and dynamic-B launches
-        static int halo = -1;
-        if (halo < 0) { const char *e = getenv("S2D_CONV_HALO"); halo = e ? atoi(e) : 1; }
-        // 3 x 3 / stride 1 / pad 1 on whole 32-channel blocks with static weights: the input-halo kernel
-        // ... when its 8 x 16 patches cover the image without much overhang (23 x 40 -> 24 x 48 wastes 20 %: implicit GEMM wins)
-        static int stem = -1;
-        if (stem < 0) { const char *e = getenv("S2D_CONV_STEM"); stem = e ? atoi(e) : 1; }
-        // the R50 stem geometry: its own halo kernel
-        if (stem && conv && p.KH == 7 && p.KW == 7 && p.stride == 2 && p.pad == 3 && p.Cin == 4 && p.N <= 64 && p.N > 32 && p.Bsplit && batch == 1 &&
-            ((p.N | p.ldc | p.ldr) & 3) == 0 && !p.res_rows && p.res_cols == p.N && !p.gate && (long)p.Hin * p.Win * 16L * (p.M / ((long)p.Hout * p.Wout)) < 0x7fffffffL)
-            return launch_conv7x7s2_stem(p, st);
-        static int halo64 = -1;
-        if (halo64 < 0) { const char *e = getenv("S2D_CONV_HALO64"); halo64 = e ? atoi(e) : 1; }
-        const int ph = p.N <= 64 ? 16 : HT_H;                 // Cout <= 64: 16 x 16 patches x 64 channels
-        if (halo && conv && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.Cin % 32 == 0 && p.Bsplit && batch == 1 && (p.N > 64 || (halo64 && p.N > 32)) &&
-            ((p.N | p.ldc | p.ldr) & 3) == 0 && !p.res_rows && p.res_cols == p.N && !p.gate &&
-            (halo == 2 || (long)p.Hin * p.Win * 100 >= (long)cdiv(p.Hin, ph) * ph * cdiv(p.Win, HT_W) * HT_W * 88))
-            return launch_conv3x3_halo(p, st);
-        static int hi = -1;
-        if (hi < 0) { const char *e = getenv("S2D_GEMM_HI"); hi = e ? atoi(e) : 2; }
-        bool use_hi;
-        if (hi != 2) use_hi = hi == 1;
-        else if (conv && p.KH > 1) use_hi = p.N <= 64;     // N <= 64: half a 128-wide tile would idle
-        else if (p.N <= 64 || p.K <= 128 || !p.Bsplit) use_hi = true;
-        else if (p.K >= 512) use_hi = false;
-        else {
-            const float w128 = (float)(cdiv(p.N, 128) * 128) / p.N, w64 = (float)(cdiv(p.N, 64) * 64) / p.N;
-            use_hi = w128 > w64 + 0.1f;
-        }
-        if (use_hi) return conv ? launch_f16_hi<true>(p, batch, st) : launch_f16_hi<false>(p, batch, st);
-        static int pipe = -1;
-        if (pipe < 0) { const char *e = getenv("S2D_GEMM_PIPE"); pipe = e ? atoi(e) : 1; }   // measured +6..12 %
-        if (pipe) return conv ? launch_f16<true, true>(p, batch, st) : launch_f16<false, true>(p, batch, st);
-        return conv ? launch_f16<true, false>(p, batch, st) : launch_f16<false, false>(p, batch, st);
-    }
-    static int w128 = -1;
-    if (w128 < 0) { const char *e = getenv("S2D_GEMM_W128"); w128 = e ? atoi(e) : 1; }
-    // 128 x 64 per wave: GEMMs with enough tiles for two workgroups per CU (the implicit-GEMM form needs more address registers
-    // than the 256-register budget leaves and spills: convolutions stay on the 64 x 64 kernels)
-    if (w128 && !conv && (long)cdiv(p.M, 256) * cdiv(p.N, BN) * batch >= (w128 == 2 ? 1 : 512)) return launch_w128<false>(p, batch, st);
-    static int force = -1;
-    if (force < 0) { const char *e = getenv("S2D_GEMM_WM"); force = e ? atoi(e) : 0; }
-    bool big = (long)cdiv(p.M, 256) * cdiv(p.N, BN) * batch >= 256;
-    if (force == 2) big = false;
-    if (force == 4) big = true;
-    if (big) return conv ? launch_t<4, true>(p, batch, st) : launch_t<4, false>(p, batch, st);
-    return conv ? launch_t<2, true>(p, batch, st) : launch_t<2, false>(p, batch, st);
+#include "gemm_route_describe.h"   // test hook (not in include/s2d_hip.h): the route of a launch described by plain integers, as text; no HIP calls
+extern "C" int s2d_gemm_route_describe(const long *launch, int flags, const int *switches, char *out, int out_len)
+{
+    return s2d_gemm_route_text(launch, flags, switches, out, out_len);
 }

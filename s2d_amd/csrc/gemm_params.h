@@ -1,6 +1,6 @@
-// Parameter block shared by the dense-contraction kernels (gemm.hip: fp32-input MFMA, gemm_bf16.hip: split-bf16).
+// Parameter block shared by the dense-contraction kernels (gemm.hip: fp32-input MFMA, gemm_bf16.hip: split-bf16).  Pointers and integers
+// only: a plain host compile can include it (gemm_route.h, the dispatch decision, does).
 #pragma once
-#include <hip/hip_runtime.h>
 
 struct GemmParams {
     const float *A, *B;
@@ -38,12 +38,12 @@ struct GemmParams {
     const float *zeros, *ones;
 };
 
-
+#ifdef __HIPCC__   // the launchers: HIP translation units only
+struct GemmSwitches;   // gemm_route.h
 int s2d_split_weights_launch(const float *W, int N, int K, long ldw, unsigned int *out, hipStream_t st, int bf16);
 int s2d_launch_gemm_bf16x3(const GemmParams &p, bool conv, int batch, hipStream_t st, int f16);
 // gemm_small.hip: one-round-trip kernel for launches of a handful of rows (M <= 256) against static pre-split weights
-bool s2d_gemm_small_m_ok(const GemmParams &p, bool conv, int batch, int f16);
 int s2d_launch_gemm_small_m(const GemmParams &p, hipStream_t st);
 // gemm_rows.hip: short K (<= 256) against static pre-split weights, a workgroup keeps its split rows resident and walks the column tiles
-bool s2d_gemm_rows_ok(const GemmParams &p, bool conv, int batch, int f16);
-int s2d_launch_gemm_rows(const GemmParams &p, hipStream_t st);
+int s2d_launch_gemm_rows(const GemmParams &p, const GemmSwitches &sw, hipStream_t st);
+#endif

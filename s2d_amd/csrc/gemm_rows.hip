@@ -18,10 +18,8 @@
 // One accumulator set: at K = 256 the resident fragments (128) + accumulators (64) + weight fragments leave no room for a second
 // one under the 256 registers that two waves per SIMD allow; the stores of a tile are in flight during the next tile's MFMAs anyway.
 #include "gemm_epilogue.h"
-#include <stdlib.h>
+#include "gemm_route.h"
 #include <atomic>
-
-bool s2d_gemm_small_m_ok(const GemmParams &p, bool conv, int batch, int f16);
 
 namespace {
 
@@ -244,18 +242,11 @@ int launch_rows(const GemmParams &p, hipStream_t st)
 
 }  // namespace
 
-// what the kernel takes (the dispatcher of gemm_bf16.hip asks first; f16: the split-fp16 mode)
-bool s2d_gemm_rows_ok(const GemmParams &p, bool conv, int batch, int f16)
-{
-    const long bC = ((long)(p.M - 1) * p.ldc + p.N) * 4L, bR = p.res ? ((long)((p.res_rows ? p.res_rows : p.M) - 1) * p.ldr + p.N) * 4L : 0;
-    return f16 && !conv && batch == 1 && p.M >= 1 && p.Bsplit && !p.Asplit && !p.gate && !p.drop_thresh && p.K % 32 == 0 && p.K >= 32 && p.K <= 256 &&
-           p.N >= 128 && ((p.N | p.ldc | p.ldr | p.res_cols) & 3) == 0 && bC <= 0xFFFFFF00L && bR <= 0xFFFFFF00L;
-}
-
-int s2d_launch_gemm_rows(const GemmParams &p, hipStream_t st)
+// the launches s2d_gemm_rows_ok (gemm_route.h) admits: the dispatcher of gemm_bf16.hip asks first
+int s2d_launch_gemm_rows(const GemmParams &p, const GemmSwitches &sw, hipStream_t st)
 {
     // a launch the few-rows kernel would take today sums K in that kernel's order (K / 64 = 2 or 4 -> 2 or 4 waves of 64)
-    const bool parts = s2d_gemm_small_m_ok(p, false, 1, 1) && (p.K == 128 || p.K == 256);
+    const bool parts = s2d_gemm_small_m_ok(p, false, 1, 1, sw) && (p.K == 128 || p.K == 256);
     switch (p.K / 32) {
     case 1: return launch_rows<1, false>(p, st);
     case 2: return launch_rows<2, false>(p, st);

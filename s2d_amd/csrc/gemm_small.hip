@@ -116,16 +116,7 @@ int launch_small(const GemmParams &p, hipStream_t st)
 
 }  // namespace
 
-// true when the launch qualifies (the dispatcher of gemm_bf16.hip asks first): few rows, static pre-split B, K in whole 64-wide
-// chunks per wave, a plain epilogue, 16-B aligned A rows
-bool s2d_gemm_small_m_ok(const GemmParams &p, bool conv, int batch, int f16)
-{
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("S2D_GEMM_SMALL"); on = e ? atoi(e) : 1; }
-    return on && f16 && !conv && batch == 1 && p.M >= 1 && p.M <= 256 && p.Bsplit && !p.Asplit && !p.gate && !p.drop_thresh && p.K >= 64 && p.K % 64 == 0 &&
-           (p.lda & 3) == 0 && ((reinterpret_cast<uintptr_t>(p.A) & 15) == 0);
-}
-
+// the launches s2d_gemm_small_m_ok (gemm_route.h) admits: the dispatcher of gemm_bf16.hip asks first
 int s2d_launch_gemm_small_m(const GemmParams &p, hipStream_t st)
 {
     const int chunks = p.K / 64;

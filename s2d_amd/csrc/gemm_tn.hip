@@ -257,11 +257,7 @@ __global__ __launch_bounds__(256, BNs == 128 ? 2 : 4) void gemm_tn_f16x3_kernel(
 }  // namespace
 
 // S2D_TN_MFMA16 (read per call; A/B runs in one process): 1 = the 16x16x32 form of the matrix instructions, 0 = 32x32x16
-static bool tn_mfma16()
-{
-    const char *e = getenv("S2D_TN_MFMA16");
-    return e ? atoi(e) != 0 : false;
-}
+static bool tn_mfma16() { return s2d_env_int("S2D_TN_MFMA16", 0) != 0; }
 
 extern "C" int s2d_gemm_tn_f32(const float *A, const float *B, float *C_slices, int Mo, int No, long rowsA, long rowsB, long lda, long ldb,
                                long chunk, long slice_stride, float *colsum_slices, hipStream_t stream)
@@ -278,8 +274,7 @@ extern "C" int s2d_gemm_tn_f32(const float *A, const float *B, float *C_slices, 
     TnParams p{};
     p.A = A; p.B = B; p.C = C_slices; p.Mo = Mo; p.No = No; p.rowsA = rowsA; p.rowsB = rowsB; p.lda = lda; p.ldb = ldb; p.chunk = chunk;
     p.sC = slice_stride; p.colsum = colsum_slices;
-    static int wide = -1;                                   // S2D_TN_WIDE=0: the 128 x 64 tile for every shape (A/B runs)
-    if (wide < 0) { const char *e = getenv("S2D_TN_WIDE"); wide = e ? atoi(e) : 1; }
+    static const int wide = s2d_env_int("S2D_TN_WIDE", 1);  // 0: the 128 x 64 tile for every shape (A/B runs)
     const bool mf16 = tn_mfma16();
     if (wide && No >= 128) {
         if (mf16) hipLaunchKernelGGL((gemm_tn_f16x3_kernel<128, false, true>), dim3(cdiv(Mo, 128) * cdiv(No, 128), (int)S), dim3(256), 0, stream, p);

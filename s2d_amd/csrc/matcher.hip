@@ -892,10 +892,8 @@ static int matcher_cost_impl(const float *mask_logits, const float *class_logits
     }
     // opt-in (read per call): measured slower, profiles/r3_experiments/not_adopted.txt -- four point groups per wave read four staged
     // logit rows at once and every row starts at bank 0
-    int q16 = 0;
-    if (const char *e = getenv("S2D_MATCHER_Q16")) q16 = atoi(e);
-    int mix = Q > 96 && Q <= 112;                           // three 32-query tiles + one 16-query tile (S2D_MATCHER_MIX=0: four 32-query tiles)
-    if (const char *e = getenv("S2D_MATCHER_MIX")) mix = mix && atoi(e);
+    const int q16 = s2d_env_int("S2D_MATCHER_Q16", 0);
+    const int mix = Q > 96 && Q <= 112 && s2d_env_int("S2D_MATCHER_MIX", 1);   // three 32-query tiles + one 16-query tile (S2D_MATCHER_MIX=0: four 32-query tiles)
     if (q16) hipLaunchKernelGGL(matcher_cost_f16_q16_kernel, dim3(grid), dim3(64 * max(4, cdiv(Q, 16))), lds_rows, stream, p);
     else if (mix) hipLaunchKernelGGL(matcher_cost_f16_mix_kernel, dim3(grid), dim3(256), lds_rows, stream, p);
     else hipLaunchKernelGGL(matcher_cost_f16_kernel, dim3(grid), dim3(256), lds_rows, stream, p);

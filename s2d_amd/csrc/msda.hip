@@ -1858,14 +1858,10 @@ int s2d_msda_fused_forward_f32(const float *value, int ldv, const int64_t *shape
     if (ldv < 0)      // experiment switch of scripts/mb_msda.py: ldv = -1 reads a head-major value tensor [N][M][S][32]
         hipLaunchKernelGGL((msda_fused_kernel<12, true>), dim3(nb, N), dim3(256), 0, stream, value, 32, lv, offs_logits, ldoa, S, M, L, P, nb, out);
     else {
-        static int share = -1, tiled = -1;
-        if (share < 0) { const char *e = getenv("S2D_MSDA_SHARE"); share = e ? atoi(e) : 1; }
-        if (tiled < 0) { const char *e = getenv("S2D_MSDA_TILED"); tiled = e ? atoi(e) : 1; }
+        static const int share = s2d_env_int("S2D_MSDA_SHARE", 1), tiled = s2d_env_int("S2D_MSDA_TILED", 1);
         // opt-in (S2D_MSDA_WIN=1; read per call: tests and scripts/mb_msda_win.py switch it inside one process): faster only while
         // the offsets are as regular as at initialisation, see profiles/r3_experiments/not_adopted.txt
-        int winmode = 0, winR = 4;
-        if (const char *e = getenv("S2D_MSDA_WIN")) winmode = atoi(e);
-        if (const char *r = getenv("S2D_MSDA_WIN_R")) winR = min(max(atoi(r), 1), 8);
+        const int winmode = s2d_env_int("S2D_MSDA_WIN", 0), winR = min(max(s2d_env_int("S2D_MSDA_WIN_R", 4), 1), 8);
         int lq = 0;
         for (int l = 1; l < L; ++l) if ((long)lv.H[l] * lv.W[l] > (long)lv.H[lq] * lv.W[lq]) lq = l;
         // opt-in (S2D_MSDA_HEAD=1, read per call): one head per workgroup with the coarsest level's plane of that head in LDS
@@ -1873,8 +1869,7 @@ int s2d_msda_fused_forward_f32(const float *value, int ldv, const int64_t *shape
         // (0.77-0.80 vs 0.66-0.72 ms): profiles/r4_experiments/not_adopted.txt
         int ls = 0;
         for (int l = 1; l < L; ++l) if ((long)lv.H[l] * lv.W[l] < (long)lv.H[ls] * lv.W[ls]) ls = l;
-        bool head_ok = false;
-        if (const char *e = getenv("S2D_MSDA_HEAD")) head_ok = atoi(e) != 0 && L > 1 && (long)lv.H[ls] * lv.W[ls] * 128 <= 150 * 1024 && (ldv & 3) == 0;
+        const bool head_ok = s2d_env_int("S2D_MSDA_HEAD", 0) != 0 && L > 1 && (long)lv.H[ls] * lv.W[ls] * 128 <= 150 * 1024 && (ldv & 3) == 0;
         WinGeo wg;
         // the windowed kernel takes the last level's queries when that level is the finest and holds most of the pyramid
         bool win_ok = winmode && tiled && M == 8 && L == 3 && P == 4 && lq == L - 1 && 2L * lv.H[lq] * lv.W[lq] > S && (long)S * ldv * 4 < 0x7fffffffL;
@@ -1931,8 +1926,7 @@ int s2d_msda_fused_forward_f32(const float *value, int ldv, const int64_t *shape
             int ntile = 0;
             for (int l = 0; l < L; ++l) ntile += ((lv.W[l] + 3) / 4) * ((lv.H[l] + 3) / 4);
             // record form (default; S2D_MSDA_REC=0: the TILED form, 2: the record form at 4 waves per SIMD / 128 registers), read per call
-            int recmode = 1;
-            if (const char *e = getenv("S2D_MSDA_REC")) recmode = atoi(e);
+            const int recmode = s2d_env_int("S2D_MSDA_REC", 1);
             const long fb = ((long)(S - 1) * ldv + (long)M * D) * 4;           // bytes of one frame's value slice as the kernel addresses it
             if (recmode && L == 3 && P == 4 && fb < 0x7fffffffL && (long)lv.start[L - 1] * ldv * 4 < 0x7fffffffL) {
                 static S2dDevOnce attr;
@@ -1984,8 +1978,7 @@ int s2d_msda_fused_backward_query_f32(const float *value, int ldv, const int64_t
     // 4 waves per SIMD, four samples' loads in flight: 3.98 ms per encoder layer's whole backward at c4 against 4.56 with the loc + chain
     // pair.  The 8-wave form (S2D_MSDA_BWD_WAVES=8, read per call; the forward's choice) needs 6 spilled registers and 28 B of scratch
     // per lane at its 64-register budget and runs at 11.8 ms (profiles/r5_experiments/not_adopted.txt).
-    int waves = 4;
-    if (const char *e = getenv("S2D_MSDA_BWD_WAVES")) waves = atoi(e);
+    const int waves = s2d_env_int("S2D_MSDA_BWD_WAVES", 4);
     if (waves != 8)
         hipLaunchKernelGGL((msda_fused_bwd_rec_kernel<3, 4, 4>), dim3(ntile, N), dim3(1024), 16 * 12 * REC_ROW, stream, value, ldv, lv, offs_logits, ldoa, grad_out, S, ntile,
                            d_offs_logits, ldd, (unsigned int)fb);

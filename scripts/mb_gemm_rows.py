@@ -1,6 +1,6 @@
 """The short-K static-weight GEMM launches of the c4 step, each in isolation, with the row-resident kernel off and forced
 (S2D_GEMM_ROWS=0 / 2, read per launch): python scripts/mb_gemm_rows.py [rounds] -> ms per launch, median over the rounds, both settings
-alternating in one process.  This table decides gemm_rows_wins() in csrc/gemm_bf16.hip."""
+alternating in one process.  This table decides gemm_rows_wins() in csrc/gemm_route.h."""
 import os
 import statistics
 import sys
