@@ -1217,6 +1217,41 @@ int s2d_plane_clean_ragged(const uint32_t *bits, const long *plane, int P, long 
                            int keep_largest, int max_hole_area, const int *tiles, int n_tiles, uint32_t *out, int *removed,
                            int *filled, void *workspace, hipStream_t stream);
 
+/* ---- binary morphology of ragged bit planes (s2d_amd/plane_morph.py) ---------------------------------------- */
+
+/* bits, plane, P and total_words are a chunk as above.  radius DEVICE i32 [P] is the radius of every plane, 0 .. 64 (0: the plane is
+ * copied with its padding zeroed; a plane with a radius outside the range is skipped, as one that does not fit the buffer is).  The
+ * rule is the project's own, stated once in s2d_amd/plane_morph.py: structuring element B(r, shape) = the disk {dx^2 + dy^2 <= r^2}
+ * (shape 0) or the square {|dx|, |dy| <= r} (shape 1); dilate (op 1): a pixel is set iff a set pixel lies in p + B, nothing outside
+ * the image is set; erode (op 0): a pixel is set iff every pixel of p + B INSIDE the image is set; open (op 2) = dilate(erode(.));
+ * close (op 3) = erode(dilate(.)).  Disks do not compose, so there is no radius over 64 and no chained pass.
+ * s2d_plane_morph_tile: the tile a workgroup handles at radius r (0 .. 64): at most `rows` rows of at most `words` row-aligned
+ * 32-pixel words; a plane of H rows is cut evenly into ceil(H / rows) tile rows of ceil(H / that) rows.  tiles DEVICE i32
+ * [n_tiles][3] = {plane, tile row, tile column} lists every tile of every plane with a radius > 0 once (host-built; the grid is 1-D
+ * over it); a row that names no tile of its plane is skipped.  Pure host code.
+ * s2d_plane_morph_lds_words: the LDS words the largest tile of an H x W plane at radius r needs (0 at r = 0, at most 10240 = 40 KiB,
+ * four workgroups per CU); -1 for a size below 1 or a radius outside 0 .. 64.  Pure host code.  lds_words of the call below is ONE
+ * figure per launch, the largest of these over the planes of the chunk: dynamic LDS, so a chunk of small masks at small radii
+ * reserves a few KiB per workgroup.  A tile that needs more than lds_words is skipped.
+ * s2d_plane_morph_workspace_bytes: the scratch the call needs (any address): 4 bytes per word of the buffer; -1 for a negative size.
+ * s2d_plane_morph_ragged writes out = op(plane) for every plane: padding bits 0, words of out that belong to no plane not written.
+ * cleared i32 [P] = popcount(in & ~out), set i32 [P] = popcount(out & ~in) over the pixels of each plane (integer sums of one
+ * workgroup per plane: deterministic; 0 for a skipped plane).  A tile reads the halo its neighbours own, so out must overlap neither
+ * bits nor the workspace, nor the workspace bits: S2D_ERR_ARG, as for an op outside 0 .. 3, a shape other than 0 or 1, a negative
+ * size, an lds_words outside 0 .. 10240 (or none with n_tiles > 0), a NULL pointer (tiles with n_tiles = 0 excepted) or a misaligned
+ * array, before anything is launched.  open and close are two passes through the workspace.  Plain stores and integer atomicOr
+ * only; the call only enqueues.
+ * s2d_plane_diff_counts_ragged: the same two counts for any two buffers a, b of the chunk (they may be one): cleared[p] = popcount(a &
+ * ~b), set[p] = popcount(b & ~a) over the pixels of plane p, padding bits of either ignored, 0 for a plane that does not fit. */
+int s2d_plane_morph_tile(int r, int *rows, int *words);
+long s2d_plane_morph_lds_words(int r, int H, int W);
+long s2d_plane_morph_workspace_bytes(long total_words, int P);
+int s2d_plane_morph_ragged(const uint32_t *bits, const long *plane, int P, long total_words, int op, int shape, const int *radius,
+                           const int *tiles, int n_tiles, int lds_words, uint32_t *out, int *cleared, int *set, void *workspace,
+                           hipStream_t stream);
+int s2d_plane_diff_counts_ragged(const uint32_t *a, const uint32_t *b, const long *plane, int P, long total_words, int *cleared,
+                                 int *set, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

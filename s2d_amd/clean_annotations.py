@@ -2,13 +2,19 @@
 cleanup of s2d_amd/plane_components.py on the device, and the masks it changed are written back as compressed RLE.
 
     python -m s2d_amd.clean_annotations --ann in.json --save-path out.json [--min-component-area N] [--keep-largest]
-        [--fill-holes N|all] [--component-connectivity 4|8] [--area-rule pixels|bbox]
+        [--fill-holes N|all] [--component-connectivity 4|8] [--open R] [--close R] [--smooth-shape disk|square]
+        [--area-rule pixels|bbox]
 
-The masks of a results.json come from thresholded logits: they carry speckle and pinholes, every self-training round feeds them back,
-and the tight boxes the merges write grow with every stray blob.  The rule is plane_components.py's -- fill(filter(mask)): components
-under --min-component-area pixels go (with --keep-largest all but the largest), then holes of at most --fill-holes pixels are set --
-and it is THIS PROJECT'S OWN: the reference cleans nothing, so with every option off (the default) nothing is launched and the
-document is returned as it came.  The same options are on `python -m s2d_amd.selftrain`, `s2d_amd.selftrain_video` and
+The masks of a results.json come from thresholded logits: they carry speckle and pinholes, whiskers and cracks, every self-training
+round feeds them back, and the tight boxes the merges write grow with every stray blob.  The rule is fill(filter(close(open(mask)))).
+Smoothing first (plane_morph.py states it): --open R removes what a disk (or square) of radius R does not fit into -- a 1-pixel
+whisker on an object, which no component rule sees --, then --close R closes the cracks and bays it does not fit into; R is N pixels
+or X% of the image diagonal (the rule of the Boundary IoU band), at most 64 pixels, and the border rule keeps a mask at the image edge
+whole.  Then plane_components.py's fill(filter(.)) on the smoothed mask: components under --min-component-area pixels go (with
+--keep-largest all but the largest), then holes of at most --fill-holes pixels are set, so what is written still has no component
+under the one and no hole up to the other; the connectivity option does not touch the smoothing.  The rule is THIS PROJECT'S OWN: the
+reference cleans nothing, so with every option off (the default) nothing is launched and the document is returned as it came.  The
+same options are on `python -m s2d_amd.selftrain`, `s2d_amd.selftrain_video` and
 `s2d_amd.keymask.results_to_annotations` (add_cleanup_arguments / cleanup_options), where the cleanup is a post-pass over the
 merged document just before it is written: the merge and keep rules see the masks as they came.
 
@@ -22,9 +28,10 @@ What is written:
   * a frame that becomes empty becomes None in `segmentations`, `bboxes` and `areas`; an annotation with no set pixel left is dropped;
     ids are never renumbered; `iscrowd = 1` annotations are left alone.
 
-Device side, per chunk of masks of different sizes: stage (rle_ragged.stage_rle_ragged), decode (decode_ragged), clean in place
-(ops.clean_planes), one read-back of the per-plane removed / filled counts, then encode_ragged over the planes with removed + filled
-> 0 only, whose count pass also gives their areas and tight boxes.  Device memory is bounded by CLEAN_CHUNK_WORDS plus the largest
+Device side, per chunk of masks of different sizes: stage (rle_ragged.stage_rle_ragged), decode (decode_ragged), with smoothing on
+ops.morph_planes at the per-plane radii and the per-plane difference to the decoded plane (plane_morph.plane_diff_counts), clean in
+place (ops.clean_planes), one read-back of the per-plane counts, then encode_ragged over the planes with a non-zero count only,
+whose count pass also gives their areas and tight boxes.  Device memory is bounded by CLEAN_CHUNK_WORDS plus the largest
 single plane, never by the file: a plane over the bound is a chunk of its own."""
 import argparse
 import json
@@ -37,6 +44,7 @@ CLEAN_CHUNK_WORDS = 5 << 19      # 2.6 M words = 84 M pixels: 12 bytes per pixel
 FILL_ALL = 2 ** 31 - 1
 AREA_RULES = ("pixels", "bbox")
 STAT_KEYS = ("planes", "planes_changed", "pixels_removed", "pixels_filled", "annotations_dropped", "frames_emptied")
+SMOOTH_STAT_KEYS = ("pixels_opened", "pixels_closed")      # beside STAT_KEYS when --open / --close is on: original vs smoothed mask
 
 
 # ---------------------------------------------------------------------------------------------------------------- options
@@ -49,14 +57,28 @@ def _fill_holes(text):
     return v
 
 
+def _radius(text):
+    from .plane_morph import parse_radius
+    try:
+        r = parse_radius(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return r if isinstance(r, int) else str(text).strip()
+
+
 def add_cleanup_arguments(ap):
-    """the four cleanup options, the same on every command line that writes an annotation file"""
+    """the cleanup options, the same on every command line that writes an annotation file"""
     g = ap.add_argument_group("mask cleanup (this project's own; off by default: the reference cleans nothing)")
     g.add_argument("--min-component-area", type=int, default=0, help="remove connected components of fewer pixels (0: off)")
     g.add_argument("--keep-largest", action="store_true", help="keep only the largest component of every mask")
     g.add_argument("--fill-holes", type=_fill_holes, default=0, metavar="N|all", help="fill holes of at most N pixels (0: off)")
     g.add_argument("--component-connectivity", type=int, choices=(4, 8), default=8,
                    help="connectivity of the set pixels; holes use the complementary one")
+    g.add_argument("--open", type=_radius, default=0, metavar="R", dest="open_radius",
+                   help="morphological opening at radius R before the component rules: N pixels or X%% of the image diagonal (0: off)")
+    g.add_argument("--close", type=_radius, default=0, metavar="R", dest="close_radius",
+                   help="morphological closing at radius R after the opening: N pixels or X%% of the image diagonal (0: off)")
+    g.add_argument("--smooth-shape", choices=("disk", "square"), default="disk", help="structuring element of --open / --close")
     return ap
 
 
@@ -64,29 +86,52 @@ def cleanup_options(args):
     """parsed arguments -> the keyword arguments of clean_document, checked"""
     opts = {"min_component_area": args.min_component_area, "keep_largest": bool(args.keep_largest), "fill_holes": args.fill_holes,
             "component_connectivity": args.component_connectivity}
+    smooth = _smooth_options(getattr(args, "open_radius", 0), getattr(args, "close_radius", 0), getattr(args, "smooth_shape", "disk"))
+    if smooth:                                                           # with both radii 0 the dict is the four keys it always was
+        opts.update(open_radius=smooth[0], close_radius=smooth[1], smooth_shape=smooth[2])
     _options(**opts)
     return opts
 
 
-def _options(min_component_area=0, keep_largest=False, fill_holes=0, component_connectivity=8):
+def _smooth_options(open_radius=0, close_radius=0, smooth_shape="disk"):
+    """-> () when both radii are 0, else (open_radius, close_radius, smooth_shape), checked: a radius is N or "X%" (plane_morph)"""
+    from .plane_morph import SHAPES, parse_radius
+    if smooth_shape not in SHAPES:
+        raise ValueError(f"smooth_shape {smooth_shape!r}: one of {SHAPES}")
+    if not (parse_radius(open_radius) > 0 or parse_radius(close_radius) > 0):
+        return ()
+    return open_radius, close_radius, smooth_shape
+
+
+def _options(min_component_area=0, keep_largest=False, fill_holes=0, component_connectivity=8, open_radius=0, close_radius=0,
+             smooth_shape="disk"):
+    """-> (min_area, keep_largest, connectivity, max_hole_area), and with a non-zero radius + (open_radius, close_radius, smooth_shape)"""
     from .plane_components import component_hole_options
     return component_hole_options({"min_component_area": min_component_area, "keep_largest": keep_largest,
-                                   "component_connectivity": component_connectivity, "max_hole_area": fill_holes})
+                                   "component_connectivity": component_connectivity, "max_hole_area": fill_holes}) \
+        + _smooth_options(open_radius, close_radius, smooth_shape)
 
 
 def cleanup_is_on(opts):
     """does a cleanup_options dict (or None) ask for anything"""
     if not opts:
         return False
-    min_area, largest, _, hole = _options(**opts)
-    return min_area > 0 or largest or hole > 0
+    return _is_on(_options(**opts))
+
+
+def _is_on(opts):
+    return opts[0] > 0 or opts[1] or opts[3] > 0 or len(opts) > 4
 
 
 # ---------------------------------------------------------------------------------------------------------------- device side
 def device_clean(chunk, opts, device=None, seconds=None):
     """the device side of one chunk (SimpleNamespace: segs = one list of ONE segmentation per plane, sizes, names) with opts =
     (min_area, keep_largest, connectivity, max_hole_area) -> SimpleNamespace(removed int [P], filled int [P], sel: the changed planes,
-    rles / areas / boxes: their new RLE dicts, pixel counts and tight boxes).  seconds: a dict that collects device-inclusive times."""
+    rles / areas / boxes: their new RLE dicts, pixel counts and tight boxes).  With smoothing on opts is that + (open_radius,
+    close_radius, smooth_shape): the radii become pixels per plane from chunk.sizes (a radius over 64 raises, naming the image, before
+    anything is launched), the planes are opened and closed before the clean, and the result gains opened int [P] / closed int [P]:
+    the pixels of the decoded plane the smoothing cleared / set; removed and filled count against the smoothed plane.  seconds: a
+    dict that collects device-inclusive times."""
     import torch
     from . import coco_eval, ops
     from .rle_ragged import decode_ragged, encode_ragged, stage_rle_ragged
@@ -98,21 +143,36 @@ def device_clean(chunk, opts, device=None, seconds=None):
             seconds[name] = seconds.get(name, 0.0) + time.perf_counter() - t0
         return time.perf_counter()
 
-    min_area, largest, conn, hole = opts
+    min_area, largest, conn, hole = opts[:4]
+    radii = []
+    if len(opts) > 4:
+        from .plane_morph import smooth_radius
+        radii = [np.array([smooth_radius(spec, H, W, name) for (H, W), name in zip(chunk.sizes, chunk.names)], np.int32) for spec in opts[4:6]]
     t0 = time.perf_counter()
     staged = stage_rle_ragged(chunk.segs, chunk.sizes, names=chunk.names)
     t0 = tick("stage", t0)
     dec = decode_ragged(staged, dev)
     t0 = tick("decode", t0)
-    out, removed, filled = ops.clean_planes(dec.bits, staged.plane, min_area, largest, hole, conn, out=dec.bits)
-    counts = torch.stack([removed, filled]).cpu().numpy()                # the one read-back of the clean: which planes changed
+    bits, smoothed = dec.bits, []
+    if radii:
+        from .plane_morph import plane_diff_counts
+        for op, rad in zip(("open", "close"), radii):
+            if rad.any():
+                bits = ops.morph_planes(bits, staged.plane, op, rad, opts[6])[0]
+        smoothed = list(plane_diff_counts(dec.bits, bits, staged.plane))
+        t0 = tick("smooth", t0)
+    out, removed, filled = ops.clean_planes(bits, staged.plane, min_area, largest, hole, conn, out=bits)
+    counts = torch.stack([removed, filled] + smoothed).cpu().numpy()     # the one read-back of the clean: which planes changed
     t0 = tick("clean", t0)
     sel = np.flatnonzero(counts.sum(0) > 0)
     rles, areas, boxes = encode_ragged(out, staged.plane, sel)
     tick("encode", t0)
     if seconds is not None:
         seconds["device_bytes"] = max(seconds.get("device_bytes", 0), int(torch.cuda.max_memory_allocated(dev)))
-    return SimpleNamespace(removed=counts[0], filled=counts[1], sel=sel, rles=rles, areas=areas, boxes=boxes)
+    r = SimpleNamespace(removed=counts[0], filled=counts[1], sel=sel, rles=rles, areas=areas, boxes=boxes)
+    if radii:
+        r.opened, r.closed = counts[2], counts[3]
+    return r
 
 
 # ---------------------------------------------------------------------------------------------------------------- the document
@@ -153,17 +213,21 @@ def _chunks(units):
 
 
 def clean_document(doc, min_component_area=0, keep_largest=False, fill_holes=0, component_connectivity=8, area_rule="pixels",
-                   device=None, device_fn=None, seconds=None):
+                   device=None, device_fn=None, seconds=None, open_radius=0, close_radius=0, smooth_shape="disk"):
     """a loaded COCO image or YTVIS annotation document -> (the cleaned document, stats) (module docstring).  device_fn: (chunk, opts)
     -> what device_clean returns replaces the device side, so the host logic runs without a device; seconds: a dict that collects the
-    phase times (stage, decode, clean, encode: device-inclusive; assemble).  stats: the counts named by STAT_KEYS."""
+    phase times (stage, decode, smooth, clean, encode: device-inclusive; assemble).  stats: the counts named by STAT_KEYS, and with
+    open_radius / close_radius (N, or "X%" of the image diagonal) non-zero those of SMOOTH_STAT_KEYS."""
     from .data.image_clip import detect_train_format
-    opts = _options(min_component_area, keep_largest, fill_holes, component_connectivity)
+    opts = _options(min_component_area, keep_largest, fill_holes, component_connectivity, open_radius, close_radius, smooth_shape)
+    smooth = len(opts) > 4
     if area_rule not in AREA_RULES:
         raise ValueError(f"area_rule must be one of {AREA_RULES}, not {area_rule!r}")
     stats = dict.fromkeys(STAT_KEYS, 0)
-    if not (opts[0] > 0 or opts[1] or opts[3] > 0):
+    if not _is_on(opts):
         return doc, stats
+    if smooth:
+        stats.update(dict.fromkeys(SMOOTH_STAT_KEYS, 0))
     if device_fn is None:
         device_fn = lambda chunk, o: device_clean(chunk, o, device, seconds)      # noqa: E731
     t0 = time.perf_counter()
@@ -176,7 +240,15 @@ def clean_document(doc, min_component_area=0, keep_largest=False, fill_holes=0, 
         r = device_fn(chunk, opts)
         t0 = time.perf_counter()
         removed, filled, sel = np.asarray(r.removed).reshape(-1), np.asarray(r.filled).reshape(-1), np.asarray(r.sel).reshape(-1)
-        if len(removed) != len(part) or len(filled) != len(part) or not np.array_equal(sel, np.flatnonzero(removed + filled > 0)) \
+        changed = removed + filled
+        if smooth:
+            opened, closed = np.asarray(r.opened).reshape(-1), np.asarray(r.closed).reshape(-1)
+            if len(opened) != len(part) or len(closed) != len(part):
+                raise ValueError(f"device_fn returned {len(opened)} / {len(closed)} smoothing counts for {len(part)} planes")
+            changed = changed + opened + closed
+            stats["pixels_opened"] += int(opened.sum())
+            stats["pixels_closed"] += int(closed.sum())
+        if len(removed) != len(part) or len(filled) != len(part) or not np.array_equal(sel, np.flatnonzero(changed > 0)) \
                 or not len(r.rles) == len(r.areas) == len(r.boxes) == len(sel):
             raise ValueError(f"device_fn returned {len(removed)} / {len(filled)} counts and {len(sel)} changed planes for {len(part)} planes")
         stats["planes"] += len(part)
@@ -229,7 +301,7 @@ def clean_merged(doc, cleanup, area_rule="pixels", device=None):
     if not cleanup_is_on(cleanup):
         return doc
     doc, stats = clean_document(doc, area_rule=area_rule, device=device, **cleanup)
-    print("Cleanup: " + "; ".join(f"{stats[k]} {k.replace('_', ' ')}" for k in STAT_KEYS) + ".")
+    print("Cleanup: " + "; ".join(f"{stats[k]} {k.replace('_', ' ')}" for k in stats) + ".")
     return doc
 
 
@@ -249,7 +321,7 @@ def clean_file(ann, save_path, area_rule="pixels", device=None, device_fn=None, 
 
 
 def build_parser():
-    ap = argparse.ArgumentParser(description="Clean the masks of a COCO image or YTVIS annotation file (connected components, holes).")
+    ap = argparse.ArgumentParser(description="Clean the masks of a COCO image or YTVIS annotation file (opening / closing, connected components, holes).")
     ap.add_argument("--ann", required=True, help="the annotation JSON to clean")
     ap.add_argument("--save-path", required=True, help="where the cleaned annotation JSON is written")
     ap.add_argument("--area-rule", choices=AREA_RULES, default="pixels",
@@ -260,7 +332,7 @@ def build_parser():
 def main(argv=None):
     a = build_parser().parse_args(argv)
     doc, stats = clean_file(a.ann, a.save_path, a.area_rule, **cleanup_options(a))
-    print("Done: {} anns; ".format(len(doc["annotations"])) + "; ".join(f"{stats[k]} {k.replace('_', ' ')}" for k in STAT_KEYS) + ".")
+    print("Done: {} anns; ".format(len(doc["annotations"])) + "; ".join(f"{stats[k]} {k.replace('_', ' ')}" for k in stats) + ".")
 
 
 if __name__ == "__main__":

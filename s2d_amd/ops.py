@@ -766,6 +766,8 @@ from .index_components import component_options, component_tile, filter_componen
 # Its component_tile is re-exported as plane_component_tile: ops.component_tile is the index-map one
 from .plane_components import clean_planes, plane_components  # noqa: E402,F401
 from .plane_components import component_tile as plane_component_tile  # noqa: E402,F401
+# opening / closing of ragged bit planes at a radius per plane (s2d_plane_morph_ragged): plane_morph.py
+from .plane_morph import morph_planes, morph_tile, smooth_radius  # noqa: E402,F401
 
 
 def pack_mask_bits(masks):

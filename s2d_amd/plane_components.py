@@ -8,7 +8,8 @@ The rule (one definition: kernel, tests/plane_components_refs.py, INTEGRATION.md
 own: the reference cleans nothing.  A plane is H x W pixels, pixel i = y*W + x in word i/32, bit i%32 of its words; padding bits of
 the last word are ignored on input and 0 on output.  A component is a maximal set of pixels of one value connected under 4- or
 8-connectivity; its label is 1 + the flat index of its first pixel in raster order, its area the number of its pixels.  The cleanup
-of a plane is fill(filter(plane)):
+of a plane is fill(filter(plane)) -- in an annotation file, of the plane smoothed first by the opening and closing of plane_morph.py
+(the rule is stated there), when those are asked for:
   filter (min_area > 0 or keep_largest)  a component of set pixels is kept iff area >= min_area and, with keep_largest, it is the
          largest of its plane, among equal areas the one with the lowest first pixel; every other set pixel becomes 0;
   fill   (max_hole_area > 0)  the ZERO pixels of the filtered plane are labelled under the complementary connectivity (8 -> 4,
@@ -66,8 +67,9 @@ def component_hole_options(opts):
     return min_area, largest, conn, int(hole)
 
 
-def _chunk(name, bits, plane_table):
-    """-> (plane numpy [P, 4], plane on the device, tiles on the device, n_tiles) for a flat buffer and its table, checked"""
+def check_chunk(name, bits, plane_table):
+    """a flat buffer and its plane table (numpy, or the device tensor decode_ragged returns), checked -> (plane numpy [P, 4], plane on
+    the device): shared by the ops of this module and of plane_morph.py"""
     from . import ops
     if bits.dtype != torch.int32 or bits.dim() != 1:
         raise ValueError(f"{name} needs the flat int32 buffer of a ragged chunk, got {bits.dtype} {tuple(bits.shape)}")
@@ -85,9 +87,15 @@ def _chunk(name, bits, plane_table):
     if len(plane) and (H.min() < 1 or W.min() < 1 or (H * W).max() >= 2 ** 31 or plane[:, 0].min() < 0
                        or (plane[:, 0] + (H * W + 31) // 32).max() > bits.numel()):
         raise ValueError(f"{name}: a plane of the table does not fit the buffer of {bits.numel()} words")
-    tiles = plane_tiles(plane)
     if plane_dev is None:
         plane_dev = torch.from_numpy(plane).to(bits.device)
+    return plane, plane_dev
+
+
+def _chunk(name, bits, plane_table):
+    """-> (plane numpy [P, 4], plane on the device, tiles on the device, n_tiles) for a flat buffer and its table, checked"""
+    plane, plane_dev = check_chunk(name, bits, plane_table)
+    tiles = plane_tiles(plane)
     tiles_dev = torch.from_numpy(tiles).to(bits.device) if len(tiles) else None
     return plane, plane_dev, tiles_dev, len(tiles)
 
