@@ -1181,6 +1181,29 @@ int s2d_index_components_i32(const uint8_t *index, int N, int H, int W, int conn
 int s2d_index_filter_components_u8(const uint8_t *index, const int *labels, const int *area, int N, int H, int W, int min_area,
                                    int keep_largest, uint8_t *out, uint8_t *rgb, int *removed, void *workspace, hipStream_t stream);
 
+/* s2d_index_fill_holes_u8 fills the holes the filter above (or the model) leaves in such a map.  conn = 4 or 8 is the connectivity
+ * of the INSTANCES; the zero pixels of an image are labelled under the complementary connectivity c' (8 -> 4, 4 -> 8), as
+ * s2d_plane_clean_ragged does.  A zero component is a hole iff none of its pixels lies in row 0, row H-1, column 0 or column W-1.
+ * The owners of a hole are the ids of the non-zero pixels that are c'-neighbours of one of its pixels (every c'-neighbour of a hole
+ * outside it is an instance pixel, and exists: a hole never touches the frame border).  A hole is filled iff its area <=
+ * max_hole_area (2^31 - 1: all) AND it has exactly ONE owner k: every one of its pixels becomes k in out and, with rgb given,
+ * colors[k-1] in rgb.  A hole with two or more owners (the gap between two instances, the ring round an island of another id) stays
+ * as it is, and so does, with rgb given, a hole whose owner k > n_colors: map and picture never disagree.  Nothing but zero pixels
+ * ever changes; the rule is idempotent, raises the component count of no id and lowers no component's area.
+ * out u8 [N][H][W] may be index.  rgb u8 [N][H][W][3] may be NULL; then colors / n_colors are ignored.  colors is a DEVICE u8 array
+ * [n_colors][3], 1 <= n_colors <= 255.  filled i32 [N] = pixels set per image (zeroed by the call).
+ * s2d_index_fill_holes_workspace_bytes: the scratch the call needs (16 bytes per pixel; any address); S2D_ERR_ARG as above.
+ * The zero pixels go through the three labelling launches above (the tile is s2d_index_components_tile); a pass over the zero
+ * pixels gives every root the integer min and max of its owners' ids, plus a value above any id from a pixel on the frame border
+ * (one owner <=> max == min), aggregated per workgroup in LDS so that a frame-sized hole does not queue on one address; a pass per
+ * aligned 4-byte word writes out.  Integer atomics only, no workgroup waits for another: a second call is bitwise equal.  The call
+ * only enqueues.  conn other than 4 or 8, N, H or W < 1, H*W >= 2^31 - 1, max_hole_area < 1, a NULL pointer other than rgb (or
+ * colors with rgb NULL), n_colors outside 1..255 with rgb given or a misaligned filled return S2D_ERR_ARG before anything is
+ * launched.  Any alignment of the byte arrays and of the workspace. */
+long s2d_index_fill_holes_workspace_bytes(int N, int H, int W);
+int s2d_index_fill_holes_u8(const uint8_t *index, int N, int H, int W, int conn, int max_hole_area, uint8_t *out, uint8_t *rgb,
+                            const uint8_t *colors, int n_colors, int *filled, void *workspace, hipStream_t stream);
+
 /* ---- connected components and cleanup of ragged bit planes (s2d_amd/plane_components.py) -------------------- */
 
 /* bits u32 [total_words] and plane DEVICE int64 [P][4] = {word0, H, W, 0} are a chunk as s2d_rle_decode_ragged fills it: plane p is

@@ -32,8 +32,10 @@ writes as OUT/davis/<sequence>/<frame>.png.  OUT/global_results.csv, OUT/per-seq
 unpinned (davis_eval.py).  --min-component-area N (default 0), --keep-largest and --component-connectivity {4,8} (default 8) clean
 every map on the device before it is scored and written (ops.filter_components: of a proposal's pixels in a frame, connected
 components smaller than N pixels become background, and with --keep-largest every component but its largest); the timing line then
-counts `removed_pixels`.  They are DAVIS options: any other --test-format refuses them by name.  With the defaults no component
-kernel is launched."""
+counts `removed_pixels`.  --fill-holes N|all (default 0: off) then fills the holes of the cleaned map (ops.fill_index_holes: a zero
+region of at most N pixels that does not touch the frame border and is enclosed by ONE proposal takes its label; the zero pixels are
+connected under the complementary connectivity); the timing line then counts `filled_pixels`.  They are DAVIS options: any other
+--test-format refuses them by name.  With the defaults no component or fill kernel is launched."""
 import argparse
 import json
 import os
@@ -42,6 +44,7 @@ import time
 
 import torch
 
+from .index_components import fill_holes_argument
 
 TEST_FORMATS = ("auto", "ytvis", "coco_image", "davis")
 
@@ -73,6 +76,8 @@ def parse_args(argv=None):
                                                                 "per frame")
     ap.add_argument("--component-connectivity", type=int, choices=(4, 8), default=None, help="davis: pixel connectivity of the "
                                                                                              "components (default 8)")
+    ap.add_argument("--fill-holes", type=fill_holes_argument, default=0, metavar="N|all",
+                    help="davis: fill holes of at most N pixels that one proposal encloses, after the cleanup (0: off)")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="config overrides KEY VALUE ...")
     return ap.parse_args(argv)
 
@@ -150,6 +155,16 @@ def component_arguments(a, fmt):
             "component_connectivity": 8 if a.component_connectivity is None else a.component_connectivity}
 
 
+def fill_arguments(a, fmt):
+    """the hole-filling option of the parsed command line -> the key it adds to the `davis` dict; with any format but davis the
+    option, if given, is refused by name"""
+    if fmt != "davis":
+        if a.fill_holes != 0:
+            raise ValueError(f"--fill-holes fills DAVIS index maps: not available with --test-format {fmt}")
+        return {}
+    return {"fill_holes": a.fill_holes}
+
+
 def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, prefetch=2, boundary=False, dilation_ratio=0.02,
                    test_format="ytvis", iou_types=None, davis=None):
     """score `model` on a YTVIS split: every video through `model([inputs])` (eval mode, predictions as COCO RLE) with the test
@@ -161,7 +176,8 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
     A directory as `gt` (test_format "davis" or "auto"): a DAVIS tree -- davis_video_document, the model's inference_index switch and
     DAVISEvaluator; `davis` = {"sequences", "rule", "max_proposals", "score_threshold", "bound_th"} (defaults: every sequence, "rank",
     20, 0.0, 0.008) and the cleanup keys "min_component_area", "keep_largest", "component_connectivity" (0, False, 8:
-    postprocess.index_map_options; the cleaned maps are the ones scored and written, the timing line gains `removed_pixels`); files
+    postprocess.index_map_options; the cleaned maps are the ones scored and written, the timing line gains `removed_pixels`) and
+    "fill_holes" (0: off; N or "all": ops.fill_index_holes after the cleanup, the timing line gains `filled_pixels`); files
     output_dir/davis/<sequence>/<frame>.png, the two CSVs and metrics.json = {"davis": the global table}.
     The model's training mode and inference switches are restored afterwards.  -> (results, timing line dict)"""
     from .data.test_loader import YTVISTestLoader
@@ -174,11 +190,13 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
     if is_davis:
         from .data.davis_loader import davis_video_document
         opt = {"sequences": None, "rule": "rank", "max_proposals": 20, "score_threshold": 0.0, "bound_th": 0.008,
-               "min_component_area": 0, "keep_largest": False, "component_connectivity": 8, **(davis or {})}
+               "min_component_area": 0, "keep_largest": False, "component_connectivity": 8, "fill_holes": 0, **(davis or {})}
         gt_dir, gt = gt, davis_video_document(image_root, gt, opt["sequences"])     # refuses a broken tree before the model runs
         index_map = {"rule": opt["rule"], "max_proposals": opt["max_proposals"], "score_threshold": opt["score_threshold"],
                      "min_component_area": opt["min_component_area"], "keep_largest": opt["keep_largest"],
                      "component_connectivity": opt["component_connectivity"]}
+        if opt["fill_holes"] != 0:                                      # a default run passes the dict it passed before
+            index_map["fill_holes"] = opt["fill_holes"]
     elif test_format == "davis":
         resolve_test_format(test_format, gt, boundary, iou_types)                    # raises: not a directory
     if isinstance(gt, str):
@@ -213,7 +231,7 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
     model.inference_rle = not is_davis
     model.inference_index = index_map
     nvid = nfr = nwin = 0
-    removed = []                                                      # device counts of the component cleanup: read after the loop
+    removed, filled = [], []                                          # device counts of the cleanup and the fill: read after the loop
     try:
         torch.cuda.synchronize(device)
         t0 = time.perf_counter()
@@ -223,6 +241,8 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
                 evaluator.process([inputs], outputs)
                 if "pred_removed" in outputs:
                     removed.append(outputs["pred_removed"])
+                if "pred_filled" in outputs:
+                    filled.append(outputs["pred_filled"])
                 nvid += 1
                 nfr += len(inputs["image"])
                 nwin += getattr(model, "last_windows", 1)
@@ -251,6 +271,8 @@ def evaluate_model(cfg, model, gt, image_root, output_dir, device, threads=8, pr
             "loader_wait_fraction": round(loader.wait_s / wall, 4) if wall > 0 else None}
     if is_davis and (opt["min_component_area"] > 0 or opt["keep_largest"]):
         line["removed_pixels"] = sum(int(r.sum()) for r in removed)
+    if is_davis and opt["fill_holes"] != 0:
+        line["filled_pixels"] = sum(int(f.sum()) for f in filled)
     return results, line
 
 
@@ -276,7 +298,7 @@ def main(argv=None):
         with open(a.gt) as fh:
             gt_doc = json.load(fh)
     fmt = resolve_test_format(a.test_format, gt_doc, a.boundary_ap, iou_types)
-    cleanup = component_arguments(a, fmt)
+    cleanup = {**component_arguments(a, fmt), **fill_arguments(a, fmt)}
     if fmt == "davis":                                                  # a broken tree is refused before the model is built
         from .data.davis_loader import davis_video_document
         from .modeling.postprocess import index_map_options

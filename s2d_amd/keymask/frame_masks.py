@@ -4,7 +4,7 @@
         --video-base-path D/DAVIS/JPEGImages/480p --mask-base-path M \\
         [--confidence-threshold 0.35] [--max-masks 50] [--frames-per-call 1] [--job-id J --videos-per-job N] [--overwrite]
         [--threads 8] [--prefetch 2] [--dataset-name NAME]
-        [--min-component-area N] [--keep-largest] [--component-connectivity {4,8}] [KEY VALUE ...]
+        [--min-component-area N] [--keep-largest] [--component-connectivity {4,8}] [--fill-holes N|all] [KEY VALUE ...]
 
 Restates what model_training/cutler/demo/demo.py does with its image model for this project's own checkpoint (one trained on image
 annotations as pseudo-clips, `train --train-format coco_image`, or any other): the instances scored at least
@@ -31,9 +31,15 @@ areas: the one whose first pixel comes first in raster order).  A removed pixel 
 underneath also holds it: the plane-free paint keeps no second owner.  With the defaults no component kernel is launched and every
 output byte is as before.
 
+--fill-holes N|all (default 0: off) then fills the holes of the cleaned owner map (ops.fill_index_holes): a region of at most N black
+pixels that does not touch the frame border and is enclosed by ONE instance -- the hole a removed speckle of another instance leaves
+in the larger one it sat on -- takes that instance's id and colour.  The black pixels are connected under the connectivity
+complementary to --component-connectivity; a region that borders two or more instances stays black.  With 0 no fill kernel is
+launched.
+
 The run ends with one JSON line on stdout: videos (folders of this job), skipped, frames (written), masks (proposals with a
 non-zero area, summed over frames), empty_frames (frames in which none has one), removed_pixels (pixels the component cleanup
-blackened; 0 with it off), wall_s, frames_per_s, loader_wait_fraction, encode_s (seconds inside PNG encoding, summed over the pool's
+blackened; 0 with it off), filled_pixels (pixels --fill-holes painted; 0 with it off), wall_s, frames_per_s, loader_wait_fraction, encode_s (seconds inside PNG encoding, summed over the pool's
 threads)."""
 import argparse
 import json
@@ -43,6 +49,7 @@ import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
 
+from ..index_components import fill_holes_argument
 from .discover import _DATASETS, make_paths, video_and_mask_dirs
 
 MAX_THREADS = 16
@@ -68,6 +75,8 @@ def parse_args(argv=None):
                                                                       "blackened (0: off)")
     ap.add_argument("--keep-largest", action="store_true", help="keep only the largest connected component of every instance per frame")
     ap.add_argument("--component-connectivity", type=int, choices=(4, 8), default=8, help="pixel connectivity of the components")
+    ap.add_argument("--fill-holes", type=fill_holes_argument, default=0, metavar="N|all",
+                    help="fill holes of at most N pixels that one instance encloses, after the cleanup (0: off)")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="config overrides KEY VALUE ...")
     return ap.parse_args(argv)
 
@@ -169,7 +178,7 @@ class _Writer:
 
 def write_masks(cfg, model, video_base_path, mask_base_path, confidence_threshold=0.35, max_masks=50, frames_per_call=1, job_id=0,
                 videos_per_job=-1, overwrite=False, threads=8, prefetch=2, dataset_name=None, device=None, min_component_area=0,
-                keep_largest=False, component_connectivity=8):
+                keep_largest=False, component_connectivity=8, fill_holes=0):
     """every clip of folder_document through `model([inputs])` (eval mode, inference_paint) and its pictures to
     mask_base_path/<video>/<frame stem>.png -> the report dict of the module docstring.  The model's training mode and inference
     switches are restored afterwards."""
@@ -177,7 +186,7 @@ def write_masks(cfg, model, video_base_path, mask_base_path, confidence_threshol
     from ..data.test_loader import YTVISTestLoader
     from ..modeling.postprocess import paint_options
     paint = {"max_masks": int(max_masks), "score_threshold": float(confidence_threshold), "min_component_area": min_component_area,
-             "keep_largest": keep_largest, "component_connectivity": component_connectivity}
+             "keep_largest": keep_largest, "component_connectivity": component_connectivity, "fill_holes": fill_holes}
     paint_options(paint)                                              # refused before anything is listed or run
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     doc, clips, counts = folder_document(video_base_path, mask_base_path, frames_per_call, job_id, videos_per_job, dataset_name,
@@ -188,7 +197,7 @@ def write_masks(cfg, model, video_base_path, mask_base_path, confidence_threshol
     model.eval()
     model.inference_rle, model.inference_device_masks, model.inference_index, model.inference_paint = False, False, None, paint
     frames = masks = empty = 0
-    removed = []                                                      # device counts: read once, after the last clip
+    removed, filled = [], []                                          # device counts: read once, after the last clip
     writer = _Writer(threads)
     try:
         torch.cuda.synchronize(device)
@@ -201,6 +210,8 @@ def write_masks(cfg, model, video_base_path, mask_base_path, confidence_threshol
                     writer.submit(out["pred_masks"], mdir, names)
                     if "pred_removed" in out:
                         removed.append(out["pred_removed"])
+                    if "pred_filled" in out:
+                        filled.append(out["pred_filled"])
                     T = len(names)
                     per_frame = [sum(1 for a in out["pred_areas"] if a[t] > 0) for t in range(T)]
                     frames += T
@@ -215,7 +226,7 @@ def write_masks(cfg, model, video_base_path, mask_base_path, confidence_threshol
         for s, v in was.items():
             setattr(model, s, v)
     return {**counts, "frames": frames, "masks": masks, "empty_frames": empty,
-            "removed_pixels": sum(int(r.sum()) for r in removed), "wall_s": round(wall, 4),
+            "removed_pixels": sum(int(r.sum()) for r in removed), "filled_pixels": sum(int(f.sum()) for f in filled), "wall_s": round(wall, 4),
             "frames_per_s": round(frames / wall, 3) if wall > 0 else None,
             "loader_wait_fraction": round(loader.wait_s / wall, 4) if wall > 0 else None, "encode_s": round(writer.encode_s, 4)}
 
@@ -227,13 +238,13 @@ def main(argv=None):
     from ..evaluate import build_model
     from ..modeling.postprocess import paint_options
     paint_options({"max_masks": a.max_masks, "score_threshold": a.confidence_threshold, "min_component_area": a.min_component_area,
-                   "keep_largest": a.keep_largest, "component_connectivity": a.component_connectivity})
+                   "keep_largest": a.keep_largest, "component_connectivity": a.component_connectivity, "fill_holes": a.fill_holes})
     cfg = load_config(a.config_file, a.opts)
     device = torch.device("cuda", torch.cuda.current_device())
     model = build_model(cfg, a.weights or cfg.MODEL.WEIGHTS, device)
     line = write_masks(cfg, model, a.video_base_path, a.mask_base_path, a.confidence_threshold, a.max_masks, a.frames_per_call,
                        a.job_id, a.videos_per_job, a.overwrite, a.threads, a.prefetch, a.dataset_name, device, a.min_component_area,
-                       a.keep_largest, a.component_connectivity)
+                       a.keep_largest, a.component_connectivity, a.fill_holes)
     print(json.dumps(line), flush=True)
     return line
 

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..index_components import COMPONENT_KEYS
+from ..index_components import COMPONENT_KEYS, FILL_KEYS
 
 
 def greedy_mask_nms(inter, labels, thr):
@@ -38,13 +38,15 @@ def greedy_mask_nms(inter, labels, thr):
 def index_map_options(index_map):
     """{"rule", "max_proposals", "score_threshold"} with the defaults ("rank", 20, 0.0) filled in; unknown keys, rules and proposal
     counts outside 1..254 are refused.  The component cleanup keys (ops.component_options: min_component_area, keep_largest,
-    component_connectivity) are known too and checked here; they are no part of the returned tuple."""
+    component_connectivity) and the hole-filling key (ops.fill_options: fill_holes) are known too and checked here; they are no part
+    of the returned tuple."""
     opts = {"rule": "rank", "max_proposals": 20, "score_threshold": 0.0}
-    unknown = set(index_map) - set(opts) - set(COMPONENT_KEYS)
+    unknown = set(index_map) - set(opts) - set(COMPONENT_KEYS) - set(FILL_KEYS)
     if unknown:
         raise ValueError(f"index_map keys {sorted(unknown)}: rule, max_proposals, score_threshold and {', '.join(COMPONENT_KEYS)} "
-                         "are known")
+                         f"are known, and {', '.join(FILL_KEYS)}")
     ops.component_options(index_map)
+    ops.fill_options(index_map)
     opts.update(index_map)
     if opts["rule"] not in ops.INDEX_RULES:
         raise ValueError(f"index_map rule {opts['rule']!r}: one of {', '.join(ops.INDEX_RULES)}")
@@ -89,19 +91,25 @@ def _inference_index(class_logits, mask_logits, dims, padded, img_size, out_size
     if min_area > 0 or largest:                                      # off: nothing is launched and no key is added
         _, removed = ops.filter_components(index, min_area, largest, conn, out=index)
         out["pred_removed"] = removed
+    max_hole = ops.fill_options(index_map)
+    if max_hole > 0:                                                 # fill(filter(map)); off: nothing is launched, no key is added
+        _, filled = ops.fill_index_holes(index, max_hole, conn, out=index)
+        out["pred_filled"] = filled
     return out
 
 
 def paint_options(paint):
     """{"max_masks", "score_threshold", "colors"} with the defaults (50, 0.35, None: ops.mask_colors) filled in; unknown keys, mask
     counts outside 1..254 and a colour table that is not u8 [>= max_masks, 3] are refused.  The component cleanup keys
-    (ops.component_options: min_component_area, keep_largest, component_connectivity) are known too and checked here; they are no
-    part of the returned tuple."""
+    (ops.component_options: min_component_area, keep_largest, component_connectivity) and the hole-filling key (ops.fill_options:
+    fill_holes) are known too and checked here; they are no part of the returned tuple."""
     opts = {"max_masks": 50, "score_threshold": 0.35, "colors": None}
-    unknown = set(paint) - set(opts) - set(COMPONENT_KEYS)
+    unknown = set(paint) - set(opts) - set(COMPONENT_KEYS) - set(FILL_KEYS)
     if unknown:
-        raise ValueError(f"paint keys {sorted(unknown)}: max_masks, score_threshold, colors and {', '.join(COMPONENT_KEYS)} are known")
+        raise ValueError(f"paint keys {sorted(unknown)}: max_masks, score_threshold, colors and {', '.join(COMPONENT_KEYS)} are known, "
+                         f"and {', '.join(FILL_KEYS)}")
     ops.component_options(paint)
+    ops.fill_options(paint)
     opts.update(paint)
     max_masks = int(opts["max_masks"])
     if not 1 <= max_masks <= ops.PAINT_MAX_PROPOSALS:
@@ -135,6 +143,10 @@ def _inference_paint(class_logits, mask_logits, dims, padded, img_size, out_size
         # owner.  pred_areas stay the areas the draw order was decided by
         _, removed = ops.filter_components(index, min_area, largest, conn, rgb=rgb, out=index)
         out["pred_removed"] = removed
+    max_hole = ops.fill_options(paint)
+    if max_hole > 0:                                                 # fill(filter(map)): a filled pixel takes its owner's colour
+        _, filled = ops.fill_index_holes(index, max_hole, conn, rgb=rgb, colors=table, out=index)
+        out["pred_filled"] = filled
     return out
 
 
@@ -155,7 +167,11 @@ def inference_video(class_logits, mask_logits, dims, padded, img_size, out_size,
     pred_scores[p]), `pred_areas` K lists of T pixel counts; not together with rle / device_masks / index_map.
     Both dicts also take "min_component_area": 0, "keep_largest": False, "component_connectivity": 8 (ops.filter_components): with an
     area above 0 or keep_largest the map is cleaned in place -- in the picture the removed pixels become black -- and `pred_removed`
-    is the CUDA int32 [T] count of removed pixels per frame; with the defaults nothing is launched and the key is absent."""
+    is the CUDA int32 [T] count of removed pixels per frame; with the defaults nothing is launched and the key is absent.
+    Both also take "fill_holes": 0 | N | "all" (ops.fill_index_holes, applied after the cleanup): every zero region of at most N
+    pixels that does not touch the frame border and is enclosed by ONE instance takes that instance's id -- and its colour in the
+    picture -- and `pred_filled` is the CUDA int32 [T] count of filled pixels per frame; with 0 nothing is launched and the key is
+    absent."""
     if paint is not None:
         if rle or device_masks or index_map is not None:
             raise ValueError("paint replaces pred_masks by one RGB picture per frame: it does not combine with rle / device_masks / "

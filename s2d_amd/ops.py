@@ -762,6 +762,8 @@ from .index_map import INDEX_MAX_PROPOSALS, INDEX_RULES, infer_index  # noqa: E4
 from .frame_paint import PAINT_MAX_PROPOSALS, infer_frame_areas, infer_paint, mask_colors, paint_frames  # noqa: E402,F401
 # connected components of those maps (s2d_index_components_i32, s2d_index_filter_components_u8): defined in index_components.py
 from .index_components import component_options, component_tile, filter_components, index_components  # noqa: E402,F401
+# hole filling in those maps (s2d_index_fill_holes_u8): index_components.py too
+from .index_components import fill_index_holes, fill_options  # noqa: E402,F401
 # connected components and cleanup of ragged bit planes (s2d_plane_components_ragged, s2d_plane_clean_ragged): plane_components.py.
 # Its component_tile is re-exported as plane_component_tile: ops.component_tile is the index-map one
 from .plane_components import clean_planes, plane_components  # noqa: E402,F401
