@@ -87,6 +87,12 @@ def _staging(n):
 # the split was losing change.  loss_scale * S is within a factor sqrt(2) of 2^GRAD_SCALE_LOG2, so the backward runs at the same
 # magnitudes whatever loss_scale (1 / ACCUM_ITER) is.  At the bench's c4 configuration the unscaled gradient operands span amax
 # 2.6e-5 .. 2.9 (scripts/split_operand_census.py, profiles/split_range/): 2^8 puts them at 6.8e-3 .. 7.3e2, inside [2^-14, 2^12].
+# The loss weights w are part of that product, and under a loss-weight schedule (loss_schedule.py) they move: a supervised weight
+# annealed to 1 % of its start would take the operands 2^-7 down, out of the window the scale was chosen for.  A model that a
+# schedule has been applied to carries loss_weight_ref = max |initial weight|; forward_backward then picks
+# S = grad_scale(loss_scale * loss_schedule.weight_rel(weights, ref)), with weight_rel the power of two nearest to
+# max |current nonzero weight| / ref, so w * loss_scale * S stays where it was at the initial weights and a common power-of-two
+# factor on all weights leaves every intermediate of the backward unchanged.  Without loss_weight_ref weight_rel is 1: nothing moves.
 GRAD_SCALE_LOG2 = int(os.environ.get("S2D_GRAD_SCALE_LOG2", "8"))
 
 

@@ -36,6 +36,10 @@ DEFAULTS = {
             "SPARSE_CLASS_WEIGHT": 0.0, "ENTROPY_WEIGHT": 0.0, "MASK_DROPLOSS": False, "LABEL_DROPLOSS": False,
             "NO_CLASS_MATCH": False, "DISTILLATION_NMS": False, "DISTILLATION_LOSS_STRATEGY": "masks-only",
             "EMA_MOMENTUM": 0.999, "EMA_MOMENTUM_SCHEDULE": False, "EMA_MOMENTUM_END": 0.999, "EMA_MOMENTUM_UNTIL_STEP": 10000,
+            # the loss-weight schedules of the reference trainer (loss_schedule.py)
+            "LOSS_WEIGHT_DECAY_STEP": 0.0, "KD_WEIGHT_SCHEDULER": "constant", "DECAY_ONLY_SUPERVISED_LOSS": False,
+            "DECAY_ONLY_KD_LOSS": False, "SUPERVISED_MIN_WEIGHT": 0.0, "KD_MIN_WEIGHT": 0.0, "KD_WEIGHT_DECAY_START": 0.0,
+            "KD_WEIGHT_DECAY_END": -1.0,
             "TEST": {"SEMANTIC_ON": True, "INSTANCE_ON": False, "PANOPTIC_ON": False, "OBJECT_MASK_THRESHOLD": 0.0,
                      "OVERLAP_THRESHOLD": 0.0, "SEM_SEG_POSTPROCESSING_BEFORE_INFERENCE": False, "USE_NMS": False,
                      "NMS_THRESH": 0.6, "NUM_PREDICTIONS": 10, "EVAL_STUDENT": False,

@@ -12,6 +12,7 @@ from torch import nn
 
 from .. import ops
 from .._lib import lib
+from ..loss_schedule import weight_rel
 from .backbone import ResNet50
 from .criterion import TargetSet, VideoHungarianMatcher, VideoSetCriterion
 from .pixel_decoder import MSDeformAttnPixelDecoder
@@ -568,7 +569,8 @@ class KDVideoMaskFormer(nn.Module):
         # reported -- or, if the walk raises, on the way out
         parts = {"predictor": list(head.predictor.parameters()), "pixel_decoder": list(head.pixel_decoder.parameters()),
                  "backbone": list(backbone.parameters())}
-        S = Bk.grad_scale(loss_scale)
+        # (times how far a loss-weight schedule has moved the weights from the ones S was chosen at; 1.0 without a schedule)
+        S = Bk.grad_scale(loss_scale * weight_rel(wd, getattr(self, "loss_weight_ref", None)))
         loss_scale = loss_scale * S
         for ctx, pre, strm in ((ctx_gt, "", crit_side), (ctx_kd, "kd_", main)):
             w_mask, w_dice = wd.get(pre + "loss_mask", 0.0), wd.get(pre + "loss_dice", 0.0)
@@ -752,7 +754,8 @@ class VideoMaskFormer(nn.Module):
                 raise NotImplementedError("per-layer loss weights that differ between decoder layers")
         from .. import backward as Bk
         params = list(self.backbone.parameters()) + list(head.parameters())
-        S = Bk.grad_scale(loss_scale)                 # the root scale of the backward (see KDVideoMaskFormer.forward_backward)
+        # the root scale of the backward (see KDVideoMaskFormer.forward_backward)
+        S = Bk.grad_scale(loss_scale * weight_rel(wd, getattr(self, "loss_weight_ref", None)))
         loss_scale = loss_scale * S
         sources = []
         if w_mask != 0.0 or w_dice != 0.0:

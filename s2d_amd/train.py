@@ -15,6 +15,16 @@ data[::-1]), data)`, :703), engine.run_step with the EMA momentum of the iterati
 EMA: a model with a teacher gets MODEL.MASK_FORMER.EMA_MOMENTUM at iteration 0; with EMA_MOMENTUM_SCHEDULE iteration i > 0 uses
 ema_momentum_schedule(i - 1, ...) (the reference updates m after it has used it, :751-768), so a resumed run recomputes it from i.
 
+Loss weights (loss_schedule.py): MODEL.MASK_FORMER.LOSS_WEIGHT_DECAY_STEP (the one-off decay of the supervised weights, :692-699) and
+KD_WEIGHT_SCHEDULER linear / cosine with KD_WEIGHT_DECAY_START / _END, SUPERVISED_MIN_WEIGHT, KD_MIN_WEIGHT, DECAY_ONLY_SUPERVISED_LOSS
+and DECAY_ONLY_KD_LOSS (:776-811) are honoured for KDVideoMaskFormer: iteration i trains with LossWeightSchedule.weights_at(i), the
+dict the reference's model sees at self.iter == i (it updates the dict after it has used it, like m).  weights_at is a pure function of
+i, so a resumed run gets the weights of the uninterrupted run; the reference restarts from the initial weights on resume.  An
+active schedule prints one JSON line at start and adds weight/<key> for the six base keys to every metrics.json record; with the
+default keys nothing is applied and every output is what it was without the schedule.  --resume also puts the per-process seed
+counters (point sampling, dropout) where the uninterrupted run has them at that iteration, so that the two runs draw the same
+points and masks.
+
 Logs: every 20 iterations (and at the last) rank 0 appends one JSON line to OUT/metrics.json in the layout of detectron2's
 JSONWriter (losses averaged over ranks, median over the window; lr and grad_norm latest; time and data_time median; data_time
 is the wait for the batch plus copy-paste, as the reference measures it).  Small collectives (seed, losses) run on the host
@@ -29,8 +39,11 @@ OUT/inference/.  An --eval-gt document with `images` and no `videos` is scored a
 AP and box AP, OUT/inference/metrics.json = {"segm", "bbox"}); a YTVIS document as before; a directory is a DAVIS annotation tree
 (--eval-image-root: JPEGImages/480p; evaluate.py --test-format davis with its defaults, metrics.json = {"davis"}).
 
-Not supported (refused): INPUT.DISENTANGLE_DISTILLATION_LOADER (the meta-archs take no distill_image) and optimizers other than
-ADAMW.  SOLVER.AMP.ENABLED is ignored with a message: the arithmetic is fp32-class, as in evaluate.py."""
+Not supported (refused): INPUT.DISENTANGLE_DISTILLATION_LOADER (the meta-archs take no distill_image), optimizers other than
+ADAMW, and of the loss-weight keys: a KD_WEIGHT_SCHEDULER other than constant / linear / cosine; linear or cosine with
+KD_WEIGHT_DECAY_END <= KD_WEIGHT_DECAY_START (the reference divides by zero) or with KD_WEIGHT_DECAY_END < SOLVER.MAX_ITER (past the
+end the reference extrapolates: supervised weights fall below their minimum and can turn negative); a negative
+SUPERVISED_MIN_WEIGHT or KD_MIN_WEIGHT.  SOLVER.AMP.ENABLED is ignored with a message: the arithmetic is fp32-class, as in evaluate.py."""
 import argparse
 import copy
 import json
@@ -80,6 +93,8 @@ def check_config(cfg, world=1):
         raise ValueError(f"SOLVER.OPTIMIZER {cfg.SOLVER.OPTIMIZER} is not supported: only ADAMW runs on the device")
     if int(cfg.SOLVER.IMS_PER_BATCH) % world:
         raise ValueError(f"SOLVER.IMS_PER_BATCH ({cfg.SOLVER.IMS_PER_BATCH}) must be divisible by the number of workers ({world})")
+    from .loss_schedule import check_schedule_config
+    check_schedule_config(cfg)
     if cfg.SOLVER.AMP.ENABLED:
         _log.warning("SOLVER.AMP.ENABLED is ignored: the library's arithmetic is fp32-class")
 
@@ -101,6 +116,25 @@ def ema_momentum_at(cfg, iteration, accum_iter=1):
     if not mf.EMA_MOMENTUM_SCHEDULE or iteration == 0:
         return float(mf.EMA_MOMENTUM)
     return float(ema_momentum_schedule(iteration - 1, mf.EMA_MOMENTUM, mf.EMA_MOMENTUM_END, mf.EMA_MOMENTUM_UNTIL_STEP, accum_iter))
+
+
+def seed_draws_per_iteration(model):
+    """the per-process seed counters one run_step call advances: (criterion.seed and matcher.seed, ops._DROP_CALLS).  Each criterion
+    call draws one point-sampling seed and one matcher seed (ground truth, and pseudo targets for a model with a teacher); every
+    deformable encoder layer in training mode with dropout draws one Philox key per forward."""
+    from .modeling.pixel_decoder import MSDeformAttnTransformerEncoderLayer
+    crit = 2 if getattr(model, "teacher", None) is not None else 1
+    drop = sum(1 for m in model.modules() if isinstance(m, MSDeformAttnTransformerEncoderLayer) and m.training and m.dropout_p > 0.0)
+    return crit, drop
+
+
+def fast_forward_seeds(model, iteration):
+    """put the seed counters where an uninterrupted run has them before `iteration`, so that a resumed run draws the same sampled
+    points and dropout masks (the counters are not part of a checkpoint: they are a function of the iteration)"""
+    from . import ops
+    crit, drop = seed_draws_per_iteration(model)
+    model.criterion.seed = model.criterion.matcher.seed = crit * int(iteration)
+    ops._DROP_CALLS[0] = drop * int(iteration)
 
 
 def save_checkpoint(out_dir, name, model, optimizer, scheduler, iteration, seed=None):
@@ -188,6 +222,7 @@ def main(argv=None):
     from .data.train_loader import YTVISTrainLoader, load_ytvis_train
     from .engine import run_step
     from .evaluate import evaluate_model
+    from .loss_schedule import BASE_KEYS, LossWeightSchedule
     from .modeling.meta_arch import META_ARCH_REGISTRY
     from .optim import build_optimizer
     from .solver import build_lr_scheduler
@@ -228,10 +263,15 @@ def main(argv=None):
     max_iter, period = int(cfg.SOLVER.MAX_ITER), int(cfg.SOLVER.CHECKPOINT_PERIOD)
     eval_period = int(cfg.TEST.EVAL_PERIOD)
     has_teacher = getattr(model, "teacher", None) is not None
+    if start_iter > 0:
+        fast_forward_seeds(model, start_iter)
+    schedule = LossWeightSchedule(cfg, model.criterion.weight_dict)
     accum = max(int(getattr(model, "accum_iter", 1)), 1)
     dl = cfg.DATALOADER
     if rank == 0:
         print(json.dumps({"start_iter": start_iter, "max_iter": max_iter, "optimizer_step": optimizer._step, "seed": seed}), flush=True)
+        if schedule.active:
+            print(json.dumps(schedule.describe()), flush=True)
 
     with open(a.train_json) as fh:
         doc = json.load(fh)
@@ -269,6 +309,7 @@ def main(argv=None):
                                       dl.COPY_PASTE_MIN_RATIO, dl.COPY_PASTE_MAX_RATIO, dl.COPY_PASTE_DENSIFY_SPARSE)
             data_time = time.perf_counter() - t_data          # as train_loop.py:702-704: the wait for the batch + copy-paste
             ema_m = ema_momentum_at(cfg, it, accum) if has_teacher else None
+            weights = schedule.apply(model, it) if schedule.active else None
             losses = run_step(model, optimizer, data, it, ema_m)
             if names is None:
                 names = sorted(losses)
@@ -295,6 +336,8 @@ def main(argv=None):
                 rec["grad_norm"] = optimizer.grad_norm() if optimizer.clip_norm > 0 else None
                 rec["time"] = statistics.median(h[2] for h in hist)
                 rec["data_time"] = statistics.median(h[3] for h in hist)
+                if weights is not None:
+                    rec.update({f"weight/{k}": weights[k] for k in BASE_KEYS if k in weights})
                 with open(os.path.join(a.output_dir, "metrics.json"), "a") as fh:
                     fh.write(json.dumps(rec) + "\n")
             if rank == 0:
