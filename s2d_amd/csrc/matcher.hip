@@ -61,7 +61,7 @@ __device__ __forceinline__ Bil bil_setup(float u, float v, int H, int W)
 struct CostParams {
     const float *ml;         // [NL][B][T*hm*wm][ldq]
     const unsigned int *tbits;   // [B][T][H][W]: bit n = target n of the clip is set at that pixel (n < min(count, 32)); the f16 kernels' target side
-    const uint8_t *tgt;      // [B][Nmax][T][H][W]
+    const uint8_t *tgt;      // [B][Nmax][T][H][W]: binary planes, nonzero = set (both kernels: a 255 is a set pixel, not a weight)
     const int *tgt_count;    // [B]
     const float *coords;     // [NL][B][P][2]  (band-sorted copy made by sort_points)
     int NL, B, Q, ldq, T, hm, wm, H, W, Nmax, P, chunks;   // chunks = T * CHM
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256) void matcher_cost_kernel(CostParams p)
                 const int k = slot + SLOTS * j;
                 float val = 0.f;
 #pragma unroll
-                for (int cnr = 0; cnr < 4; ++cnr) val += (float)pl[bti[cnr][k]] * btw[cnr][k];
+                for (int cnr = 0; cnr < 4; ++cnr) val += (pl[bti[cnr][k]] != 0 ? 1.f : 0.f) * btw[cnr][k];   // nonzero = set, as target_bits_kernel
                 val *= live;
                 Ts[k][tn] = val;
                 tsum += val;

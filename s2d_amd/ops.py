@@ -585,7 +585,11 @@ def masked_attn(q, k, v, bits=None, unmasked=None, H=8, want_lse=False):
 # ----------------------------------------------------------------------------- matcher / criterion
 def matcher_cost(mask_logits, class_logits, tgt, tgt_count, dims, P, weights, coords=None, seed=0):
     """mask_logits [NL,B,T*hm*wm,ldq] pixel-major, class_logits [NL,B,Q,C1] (C1 = classes + 1), tgt u8 [B,Nmax,T,H,W],
-    tgt_count i32 [B].  dims = (Q, T, hm, wm).  -> C [NL*B, Q, Nmax]"""
+    tgt_count i32 [B].  dims = (Q, T, hm, wm).  -> C [NL*B, Q, Nmax]
+    tgt holds binary planes: a byte is read as `!= 0` (0/1 and 0/255 masks give the same matrix, at every target count);
+    only the first min(tgt_count[b], Nmax) planes of clip b are read, and columns past that count are written as 0.
+    Layer l's problem for clip b is row l * B + b.  ldq = mask_logits.shape[-1] >= Q; columns Q .. ldq-1 are never used.
+    |logit| < 65504.  coords [NL,B,P,2] in [0,1] injects the sample points; None draws them from `seed` on the device."""
     _chk(mask_logits); _chk(class_logits); _chk(tgt, torch.uint8); _chk(tgt_count, torch.int32); _chk(coords)
     NL, B = mask_logits.shape[:2]
     Q, T, hm, wm = dims

@@ -3,6 +3,8 @@ GT criterion -> KD targets -> KD criterion) on HIP vs the CPU oracle, same seede
 import numpy as np
 import pytest
 
+from tests.matcher_refs import cost64 as _cost64   # the float64 cost matrix, shared with tests/test_gpu_matcher_paths.py
+
 pytestmark = pytest.mark.gpu
 
 
@@ -22,27 +24,6 @@ def _same_assignment(iq, it, ri, rj, C):
     assert sorted(it.tolist()) == sorted(rj.tolist()) and len(set(iq.tolist())) == len(iq)
     assert abs(ours - best) <= 2e-6 * np.abs(C).max() * len(ri), (ours, best, iq, it, ri, rj)
     TIES.append((float(ours - best), int((it != rj).sum() + (iq != ri).sum())))
-
-
-def _cost64(oracle, logits, masks, tgt, coords, wc, wm, wd):
-    """matcher.py:236-287 on the oracle's fp32 point samples (point_features.py:19-42) with the contractions and the activation
-    sums in float64: the value both fp32 implementations (the reference's einsum, the device's split-fp16 MFMA + double
-    reduction) approximate"""
-    Q, N, P = masks.shape[0], tgt.shape[0], coords.shape[1]
-    tm = oracle.point_sample(tgt, np.repeat(coords, N, 0)).reshape(N, -1).astype(np.float64)
-    om = oracle.point_sample(masks.astype(np.float32), np.repeat(coords, Q, 0)).reshape(Q, -1).astype(np.float64)
-    sp = np.maximum(om, 0) + np.log1p(np.exp(-np.abs(om)))
-    cost_mask = (sp.sum(-1)[:, None] - om @ tm.T) / om.shape[1]
-    sg = 1.0 / (1.0 + np.exp(-om))
-    cost_dice = 1 - (2 * (sg @ tm.T) + 1) / (sg.sum(-1)[:, None] + tm.sum(-1)[None, :] + 1)
-    l = logits.astype(np.float32)
-    if l.shape[-1] > 2:                                   # class-aware heads: -softmax(l)[:, 0] over all C1 columns, in float64
-        l = l.astype(np.float64)
-    e = np.exp(l - l.max(-1, keepdims=True))
-    cost_class = -np.repeat((e / e.sum(-1, keepdims=True))[:, :1].astype(np.float64), N, axis=1)
-    # second value: the magnitude of the cost's terms (the sum itself can cancel to ~0: a random-init layer whose class, mask and
-    # dice terms nearly offset has max|C| = 0.37 from terms of size 5 -- errors are measured against the terms)
-    return wm * cost_mask + wc * cost_class + wd * cost_dice, float((abs(wm) * np.abs(cost_mask) + abs(wc) * np.abs(cost_class) + abs(wd) * np.abs(cost_dice)).max())
 
 
 def _check(hip, ref, B, NL, oracle=None):
